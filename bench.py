@@ -43,6 +43,12 @@ Output: ONE JSON line on rank 0 with two extra objects:
   cpu_baseline -- the CPU oracle (a port of the reference's algorithm, oracle/) timed on this host: 1 warm-up + 3 timed
                   closures on a bounded sample of the same workload, autograd incl. weight gradients like the reference.
 Any failure while collecting either makes the run exit non-zero (after printing the line with the error recorded).
+``ms_per_step`` = wall milliseconds of one timed step (``--steps`` of them, after ``--warmup`` untimed ones).
+
+``--dump-outputs DIR`` writes, after the timed region, what rank 0's last timed step computed (the optimised latents and the
+loss; ``sample``: the sample_batched dict; ``train``: the loss entries and the updated parameters; ``full``: the per-scene
+results) as DIR/<name>.npy, so that two builds can be compared output for output: the inputs are deterministic (counter-based
+draws of strive_amd.synth; torch's generators, which `sample` and `train` draw from, are seeded with the rank).
 """
 import argparse
 import json
@@ -212,6 +218,7 @@ def refine_closure_factory(m, env, batch, map_idx, FT, device):
         opt.step()
         return ld['loss']
     step = GraphedIteration(iteration, graphed)
+    step.outputs = lambda: {'z': z}
 
     def graph_vs_eager():
         """After the timed region: from the SAME latents and Adam state, one iteration replayed from the graph and one run eagerly;
@@ -264,12 +271,15 @@ def adv_closure_factory(m, env, batch, map_idx, FT, device, on_planner_error='dr
         step = GraphedIteration(c.step, c.graphed)
         step.planner = planner
         step.closure = c
+        step.outputs = lambda: {'z': c.collated()}
         return step, emb, g, mi, 2
     c = AdvClosure(emb['posterior_out'][0].clone(), 0.05, ADV_WEIGHTS, m, g, env, mi, emb, (pm[ego], pv[ego]),
                    (pm[~ego], pv[~ego]), 2, 0.0, planner_fut=g.future_gt[ego][:, :FT, :4].contiguous(), future_len=FT,
                    veh_coll_buffer=0.1)
     from strive_amd.utils.graphed import GraphedIteration
-    return GraphedIteration(c.step, c.graphed), emb, g, mi, 2
+    step = GraphedIteration(c.step, c.graphed)
+    step.outputs = lambda: {'z': c.collated()}
+    return step, emb, g, mi, 2
 
 
 def full_pipeline_factory(m, env, batch, map_idx, FT, device, scale=1.0):
@@ -430,6 +440,8 @@ def full_pipeline_factory(m, env, batch, map_idx, FT, device, scale=1.0):
                 json.dump(d, f)
         return written
     step.write_scenarios = write_scenarios
+    step.outputs = lambda: {'init_pred': last['init'], 'final_result_traj': last['fin'], 'z': last['z'],
+                            'attack_agt': torch.as_tensor(last['agt']), 'attack_t': torch.as_tensor(last['tt'])}
     step.stats = stats
     return step, None, batch.to(device), map_idx.to(device), 2
 
@@ -439,10 +451,14 @@ def sample_step_factory(m, env, batch, map_idx, FT, device, NS=20):
     g = batch.to(device)
     mi = map_idx.to(device)
 
+    last = {}
+
     def step():
         with torch.no_grad():
             out = m.sample_batched(g, mi, env, NS, include_mean=True, nfuture=FT)
+        last['out'] = out
         return out['future_pred'].abs().mean()
+    step.outputs = lambda: dict(last['out'])
     return step, None, g, mi, NS
 
 
@@ -464,11 +480,21 @@ def train_step_factory(m, env, batch, map_idx, FT, device):
     opt = torch.optim.Adam(m.parameters(), lr=1e-5, **({'fused': True} if fused else {}))
     tr = DataParallelTrainer(m, TrafficModelLoss(TRAIN_WEIGHTS, m.get_normalizer(), m.get_att_normalizer()), opt)
 
+    last = {}
+
     def step():
         out = tr.step(g, mi, env)
         if out is None:
             raise RuntimeError('training step was skipped: %r' % (tr.last_error,))
+        last['out'] = out
         return out['global_loss'][0]
+
+    def outputs():
+        # the step's loss entries and the parameters Adam has just updated
+        res = {'loss_' + k: v for k, v in last['out'].items()}
+        res.update({'param_' + k: p for k, p in m.named_parameters()})
+        return res
+    step.outputs = outputs
     return step, None, g, mi, 2
 
 
@@ -905,6 +931,54 @@ def gather_ranks(use_dist, world, device, dt_local, units_local, rank_record):
     return dt, units, per_rank, backend
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def _dump_arrays(outputs):
+    """{name: tensor / array / number / tuple of them} -> {name: float32 or float64 numpy array}, copies on the host that share
+    no memory with the inputs.  Floating arrays keep float64 when computed in float64 and become float32 otherwise; integer and
+    boolean arrays become float64 (exact)."""
+    import numpy as np
+    res = {}
+    for name, v in outputs.items():
+        if isinstance(v, (tuple, list)) and v and not isinstance(v[0], (int, float, bool)):
+            res.update(_dump_arrays({'%s_%d' % (name, i): x for i, x in enumerate(v)}))
+            continue
+        if torch.is_tensor(v):
+            v = v.detach().cpu()
+            v = v.to(torch.float64 if v.dtype == torch.float64 or not v.is_floating_point() else torch.float32).numpy()
+        elif isinstance(v, (np.ndarray, np.generic, int, float, bool, tuple, list)):
+            v = np.asarray(v)
+            if v.dtype.kind not in 'biuf':
+                continue
+            v = v.astype(np.float32 if v.dtype.kind == 'f' and v.dtype.itemsize < 8 else np.float64)
+        else:
+            continue
+        res[name] = np.array(v, copy=True)
+    return res
+
+
+def write_outputs(out_dir, outputs, limit=DUMP_LIMIT_BYTES):
+    """Write what the timed path computed in its last step as out_dir/<name>.npy.  Above `limit` bytes in all, the limit is shared
+    out from the smallest array up (each takes at most an even share of what is left) and every array that does not fit its share
+    is replaced by a fixed sample of its flattened entries (the same positions in every run with the same arguments), written as
+    <name>.sample.npy.  -> {file name: shape}"""
+    import numpy as np
+    arrays = _dump_arrays(outputs)
+    os.makedirs(out_dir, exist_ok=True)
+    left, written = limit - 1024 * len(arrays), {}         # (1 KB per file for its .npy header)
+    for i, name in enumerate(sorted(arrays, key=lambda k: (arrays[k].nbytes, k))):
+        a, fn = arrays[name], name + '.npy'
+        share = left // (len(arrays) - i)
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=share // a.itemsize, replace=False))
+            a, fn = a.reshape(-1)[idx], name + '.sample.npy'
+        left -= a.nbytes
+        np.save(os.path.join(out_dir, fn), a)
+        written[fn] = list(a.shape)
+    return dict(sorted(written.items()))
+
+
 def _free_port():
     s = socket.socket()
     s.bind(('127.0.0.1', 0))
@@ -941,7 +1015,12 @@ def parse_args(argv=None):
     ap.add_argument('--no-roofline', action='store_true')
     ap.add_argument('--dry-run', action='store_true', help='CPU/gloo: join the ranks, build the scene partition, no kernels')
     ap.add_argument('--fail-rank', type=int, default=-1, help='dry run only (test hook): this rank raises before the collectives')
+    ap.add_argument('--dump-outputs', default='', metavar='DIR',
+                    help="after the timed steps, write what rank 0's last timed step computed (the arrays its caller receives: "
+                         "latents, loss, predictions) as DIR/<name>.npy, float32 or float64, at most 64 MB in all")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
     if not args.nc:
         args.nc = 5 if args.workload == 'sharded4096' else 2
     if not args.ft:
@@ -982,6 +1061,9 @@ def main():
     if use_dist:
         dist.barrier()
 
+    # the workloads are built from counter-based draws (strive_amd.synth); the posterior / prior samples of `sample` and `train`
+    # come from torch's generators, which start at a different seed in every process unless seeded here
+    torch.manual_seed(rank)
     own, desc, scaling = workload_scenes(args, rank, world)
     lane_graph = None
     if args.workload == 'full':
@@ -1024,6 +1106,11 @@ def main():
     dt_host_cpu = time.thread_time() - c0       # CPU time of the enqueueing thread: the wall time above also holds the waits for a
     barrier()                                   # free slot in the hardware queue once the GPU is the bottleneck
     dt_local = time.perf_counter() - t0
+    last_outputs = None
+    if args.dump_outputs and rank == 0:
+        # copied to host arrays (nested tuples included) before anything else runs on the model: graph_vs_eager replays the
+        # iteration once more
+        last_outputs = _dump_arrays(dict(step.outputs(), loss=loss))
     gve = step.graph_vs_eager() if (hip_graph and getattr(step, 'graph_vs_eager', None) is not None) else None
     if args.workload == 'full' and args.scenario_out and rank == 0:
         step.stats['scenarios_written'] = step.write_scenarios(args.scenario_out)
@@ -1129,6 +1216,8 @@ def main():
         'host': host_pin,
     }
     failed = gve is not None and not (gve[0] <= 1e-5)
+    if last_outputs is not None:
+        out['dumped_outputs'] = write_outputs(args.dump_outputs, last_outputs)
     if rank == 0:
         if not args.no_roofline and args.workload not in ('train', 'sample', 'full'):
             try:

@@ -17,8 +17,8 @@ the top of its driver scripts:
     are the reference's files with this package's implementations laid over the same names (``datasets.map_env`` stays
     the reference's: the model only reads the raster tensors it builds);
   * the loop drivers ``utils.{init,adv_gen,sol}_optim`` are this package's by default; ``loops='reference'`` keeps the
-    reference's own loop functions, which then run unchanged on top of the HIP-backed model and loss modules (that is
-    what tests/test_dropin_reference.py executes in the build container).
+    reference's own loop functions, which then run unchanged on top of the HIP-backed model and loss modules
+    (tests/test_dropin_reference.py checks both modes on a synthetic tree of the reference's layout).
 """
 import importlib
 import os

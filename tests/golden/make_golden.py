@@ -588,8 +588,8 @@ def g6_loop(R):
     save('g6_loop.npz', z=np.stack(zs), grad=np.stack(grads), losses=np.asarray(losses), loss_keys=np.asarray(keys))
 
     # the reference's own refine_traffic_optim() draws its starting sample unseeded, so it cannot be a fixture; its
-    # init / adv / sol loop functions are run as they are by g6_loops() below, and tests/test_dropin_reference.py
-    # (build container only) executes the reference's loop functions on top of this package's modules.
+    # init / adv / sol loop functions are run as they are by g6_loops() below, and g13_dropin() stores one iteration of its
+    # run_adv_gen_optim for tests/test_dropin_reference.py.
 
 
 LOOP_WEIGHTS = dict(ADV_WEIGHTS)
@@ -1052,11 +1052,45 @@ def g12_refine_fn(R):
 G8_CASES = [(15.0, 0, 0.0, None, False), (15.0, 2, 0.5, None, True), (25.0, 1, 0.0, 0.0, True), (8.0, 0, 1.0, -0.5, False)]
 
 
+DROPIN_SIZES = [3]      # every scene needs an attacker (the reference's AdvGenLoss indexes max() over them)
+DROPIN_FT = 2
+
+
+def g13_inputs():
+    """(batch, map_idx, raster, dx) of tests/test_dropin_reference.py: 3 agents, FT 2, textured raster."""
+    batch, map_idx = synth.make_batch(DROPIN_SIZES, key='dropin', FT=DROPIN_FT)
+    raster, dx = synth.make_raster(RASTER_HW, RASTER_HW)
+    return batch, map_idx, raster, dx
+
+
+def g13_dropin(R):
+    """The reference's own run_adv_gen_optim (planner 'ego'), ONE iteration from the posterior mean on the drop-in check's
+    scene: tests/test_dropin_reference.py makes the same call through the reference's import names on this package's modules."""
+    import contextlib
+    import io
+    tm, _ = ref_model(R, FT=DROPIN_FT)
+    batch, map_idx, raster, dx = g13_inputs()
+    env = ref_map_env(R, raster, dx)
+    with torch.no_grad():
+        emb = R.scenario_gen.detach_embed_info(tm.embed(batch, map_idx, env))
+    NA = batch.past.shape[0]
+    ego = torch.zeros((NA,), dtype=torch.bool)
+    ego[batch.ptr[:-1]] = True
+    pm, pv = emb['prior_out']
+    z0 = emb['posterior_out'][0].clone()
+    with contextlib.redirect_stdout(io.StringIO()), contextlib.redirect_stderr(io.StringIO()):
+        z, fin, _, agt, tt = R.adv_optim.run_adv_gen_optim(z0.clone(), 0.05, LOOP_WEIGHTS, tm, batch, env, map_idx, 1, emb, 'ego',
+                                                           (pm[ego], pv[ego]), (pm[~ego], pv[~ego]), 0, 0.0)
+    save('g13_dropin.npz', map_feat=npy(emb['map_feat']), z0=npy(z0), z=npy(z), final_result_traj=npy(fin),
+         min_agt=np.asarray(agt), min_t=np.asarray(tt))
+
+
 if __name__ == '__main__':
     torch.set_num_threads(8)
     R = import_reference()
-    which = sys.argv[1:] or ['g1', 'g2', 'g3', 'g4', 'g4u', 'g4b', 'g5', 'g6', 'g6l', 'g6h', 'g7', 'g8', 'g9', 'g10', 'g11', 'g12']
+    which = sys.argv[1:] or ['g1', 'g2', 'g3', 'g4', 'g4u', 'g4b', 'g5', 'g6', 'g6l', 'g6h', 'g7', 'g8', 'g9', 'g10', 'g11', 'g12', 'g13']
     fns = {'g1': g1_ops, 'g2': g2_crop, 'g3': g3_gnn, 'g4': g4_rollout, 'g5': g5_losses, 'g6': g6_loop, 'g7': g7_sample,
-           'g8': g8_checks, 'g9': g9_wire, 'g6l': g6_loops, 'g4b': g4b_nc5, 'g4u': g4u_rollout, 'g10': g10_planner, 'g6h': g6h_hardcode, 'g11': g11_eval, 'g12': g12_refine_fn}
+           'g8': g8_checks, 'g9': g9_wire, 'g6l': g6_loops, 'g4b': g4b_nc5, 'g4u': g4u_rollout, 'g10': g10_planner, 'g6h': g6h_hardcode, 'g11': g11_eval, 'g12': g12_refine_fn,
+           'g13': g13_dropin}
     for w in which:
         fns[w](R)
