@@ -35,15 +35,23 @@ step.  Workloads (``--workload``):
 ``python bench.py --gpus N`` launches the N ranks itself (re-executing under torch.distributed.run on 127.0.0.1) when it
 was not started by a launcher; under a launcher (WORLD_SIZE set) it is one rank of the job.
 
-Output: ONE JSON line on rank 0 with two extra objects:
-  roofline     -- the dominant kernel (a map-CNN convolution on the fp16 matrix cores), timed live with events on the
-                  launching stream, against BOTH roofs (matrix: algorithmic FLOPs x issued products / duration; HBM:
-                  algorithmic bytes / duration) -- `bound` names the one with the larger fraction;
-                  `bandwidth_kernels` = achieved GB/s of the byte-bound kernels (algorithmic bytes / live duration).
-  cpu_baseline -- the CPU oracle (a port of the reference's algorithm, oracle/) timed on this host: 1 warm-up + 3 timed
-                  closures on a bounded sample of the same workload, autograd incl. weight gradients like the reference.
-Any failure while collecting either makes the run exit non-zero (after printing the line with the error recorded).
-``ms_per_step`` = wall milliseconds of one timed step (``--steps`` of them, after ``--warmup`` untimed ones).
+Output: ONE JSON line on rank 0.  ``ms_per_step`` = wall milliseconds of one timed step (``--steps`` of them, after ``--warmup``
+untimed ones); ``value`` = agent*timesteps/s of the timed steps.
+
+A plain run does only that: set up, warm up, time the steps, write ``--dump-outputs`` and print the line.  ``--full`` adds the
+side measurements and checks, all after the timed region (the line's ``full`` field says which kind of run it is):
+  graph_vs_eager -- HIP-graph workloads: one iteration replayed from the graph against one run eagerly from the same latents and
+                    Adam state; the run fails above 1e-5.
+  planner        -- closed loop (``--planner hardcode``): the planner rollout timed on its own.
+  roofline       -- the dominant kernel (a map-CNN convolution on the fp16 matrix cores), timed live with events on the
+                    launching stream, against BOTH roofs (matrix: algorithmic FLOPs x issued products / duration; HBM:
+                    algorithmic bytes / duration) -- `bound` names the one with the larger fraction;
+                    `bandwidth_kernels` = achieved GB/s of the byte-bound kernels (algorithmic bytes / live duration).
+                    ``--no-roofline`` leaves it out.
+  cpu_baseline   -- the CPU oracle (a port of the reference's algorithm, oracle/) timed on this host: bounded samples of the same
+                    workload, autograd incl. weight gradients like the reference (about three minutes; ``--cpu-baseline-full``:
+                    C2 itself).  ``--no-cpu-baseline`` leaves it out.
+Any failure while collecting them makes the run exit non-zero (after printing the line with the error recorded).
 
 ``--dump-outputs DIR`` writes, after the timed region, what rank 0's last timed step computed (the optimised latents and the
 loss; ``sample``: the sample_batched dict; ``train``: the loss entries and the updated parameters; ``full``: the per-scene
@@ -864,7 +872,7 @@ def cpu_baseline(FT, scenes=4, agents=16, raster_px=4096, timed=3, warm=1):
 
 def cpu_baseline_record(FT, full=False):
     """The bench line's `cpu_baseline`.  SURVEY 8(d) quotes the CPU at C2 (32 scenes x 16 agents), where one closure of the
-    oracle takes minutes; the default run therefore times two bounded samples of the same workload -- 4 x 16 agents (1 warm-up + 1 timed
+    oracle takes minutes; a --full run therefore times two bounded samples of the same workload -- 4 x 16 agents (1 warm-up + 1 timed
     closure) and 16 x 16 agents (2 timed closures) -- reports the LARGER sample as `value` and states both, so the trend
     towards C2 is visible (it differs by host: 77 -> 31 agent*timesteps/s from 4 to 32 scenes on the 8-vCPU survey container,
     79 -> 90 from 4 to 16 scenes on the 128-thread EPYC of the GPU boxes).  ``--cpu-baseline-full`` times C2 itself (1 warm-up +
@@ -875,7 +883,7 @@ def cpu_baseline_record(FT, full=False):
         return rec
     # (with the reference's per-channel crop structure a 16 x 16 closure takes ~65 s on the GPU boxes' EPYC: the small sample is also
     # the process's warm-up -- thread pool, allocator, convolution primitives -- and the large one times its first two closures, both
-    # listed in `closure_s`, so that the default run stays at about three minutes of CPU work)
+    # listed in `closure_s`, so that a --full run stays at about three minutes of CPU work)
     small = cpu_baseline(FT, scenes=4, agents=16, timed=1, warm=1)
     large = cpu_baseline(FT, scenes=16, agents=16, timed=2, warm=0)
     rec = dict(large)
@@ -1010,9 +1018,12 @@ def parse_args(argv=None):
     ap.add_argument('--scenario-out', default='', help='full: directory for the scenario JSON of every scene (reference '
                     'src/adv_scenario_gen.py:465-538 -> prepare_output_dict), written from the device tensors after the timed region')
     ap.add_argument('--raster', type=int, default=4096)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--cpu-baseline-full', action='store_true', help='time the CPU oracle on C2 itself (32 x 16 agents; ~10 minutes)')
-    ap.add_argument('--no-roofline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps, also take the side measurements and checks: graph replay against eager, the planner '
+                         'alone, the roofline records and the CPU baseline (several minutes); a plain run only times the steps')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full without the CPU baseline')
+    ap.add_argument('--cpu-baseline-full', action='store_true', help='--full: time the CPU oracle on C2 itself (32 x 16 agents; ~10 minutes)')
+    ap.add_argument('--no-roofline', action='store_true', help='--full without the roofline records')
     ap.add_argument('--dry-run', action='store_true', help='CPU/gloo: join the ranks, build the scene partition, no kernels')
     ap.add_argument('--fail-rank', type=int, default=-1, help='dry run only (test hook): this rank raises before the collectives')
     ap.add_argument('--dump-outputs', default='', metavar='DIR',
@@ -1021,6 +1032,8 @@ def parse_args(argv=None):
     args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error('--steps must be at least 1')
+    if args.cpu_baseline_full and not args.full:
+        ap.error('--cpu-baseline-full belongs to --full')
     if not args.nc:
         args.nc = 5 if args.workload == 'sharded4096' else 2
     if not args.ft:
@@ -1111,7 +1124,7 @@ def main():
         # copied to host arrays (nested tuples included) before anything else runs on the model: graph_vs_eager replays the
         # iteration once more
         last_outputs = _dump_arrays(dict(step.outputs(), loss=loss))
-    gve = step.graph_vs_eager() if (hip_graph and getattr(step, 'graph_vs_eager', None) is not None) else None
+    gve = step.graph_vs_eager() if (args.full and hip_graph and getattr(step, 'graph_vs_eager', None) is not None) else None
     if args.workload == 'full' and args.scenario_out and rank == 0:
         step.stats['scenarios_written'] = step.write_scenarios(args.scenario_out)
     planner_ms = None
@@ -1126,7 +1139,8 @@ def main():
                           'limits': sorted(set(n for v in failed_scenes.values() for n in v)),
                           'note': 'units count every scene of the batch: a dropped scene is still rolled out and planned, only its '
                                   'loss terms and gradients are masked'}
-        planner_ms = time_planner(step, device)
+        if args.full:
+            planner_ms = time_planner(step, device)
     dt = dt_local
     NA = int(g.past.shape[0])
     units_local = rollouts * NA * args.ft * args.steps
@@ -1198,8 +1212,9 @@ def main():
                    'weights': ('random init (synth.fill_state_dict)' if args.planner != 'hardcode' else
                                'random init, decoder output layer scaled (acceleration x0.3, yaw acceleration x0.05: synth.lane_keeping_weights) '
                                'so that the predicted agents follow their lanes -- what the rule-based planner assumes')},
-        # the timed path (graph replay) against one eager iteration from the same latents and Adam state, after the timed region:
-        # max |z_replayed - z_eager| (and how far that iteration moved the latents); the run FAILS above 1e-5
+        'full': args.full,
+        # (--full) the timed path (graph replay) against one eager iteration from the same latents and Adam state, after the timed
+        # region: max |z_replayed - z_eager| (and how far that iteration moved the latents); the run FAILS above 1e-5
         'graph_vs_eager_max_abs': None if gve is None else gve[0],
         'graph_vs_eager_step_size': None if gve is None else gve[1],
         'final_loss': float(loss.detach().cpu()),
@@ -1218,7 +1233,7 @@ def main():
     failed = gve is not None and not (gve[0] <= 1e-5)
     if last_outputs is not None:
         out['dumped_outputs'] = write_outputs(args.dump_outputs, last_outputs)
-    if rank == 0:
+    if rank == 0 and args.full:
         if not args.no_roofline and args.workload not in ('train', 'sample', 'full'):
             try:
                 out['roofline'] = time_dominant_kernel(m, env, g, mi, emb, device)
@@ -1257,6 +1272,7 @@ def main():
             except Exception as e:
                 out['cpu_baseline'] = {'error': repr(e)}
                 failed = True
+    if rank == 0:
         print(json.dumps(out), flush=True)
     if use_dist:
         dist.barrier()

@@ -20,13 +20,13 @@ python profiles/summarize_pmc.py $(find $O/sq -name "*counter_collection.csv" | 
 python profiles/make_traffic.py $O/pmc_fetch_size.txt $O/pmc_write_size.txt $O/kernel_stats.txt > $O/traffic.json 2>> $O/fetch.log
 find $O -type f -size +1M -delete
 cp $O/traffic.json profiles/r03_traffic.json          # (this run's own counters feed bench.py's `traffic` fields below)
-python bench.py --steps 20 --warmup 5 > $O/bench_line.json 2> $O/bench.err
-$B --workload adv > $O/bench_line_adv.json 2>> $O/bench.err
-$B --workload adv --planner hardcode > $O/bench_line_adv_hardcode.json 2>> $O/bench.err
-$B --scenes 1 --agents 8 --steps 20 > $O/bench_line_1x8.json 2>> $O/bench.err
-$B --workload train --steps 10 --warmup 3 > $O/bench_line_train.json 2>> $O/bench.err
-$B --workload sample --steps 5 > $O/bench_line_sample.json 2>> $O/bench.err
-$B --workload sharded4096 --steps 5 > $O/bench_line_sharded4096_1gpu.json 2>> $O/bench.err
+python bench.py --full --steps 20 --warmup 5 > $O/bench_line.json 2> $O/bench.err
+$B --full --workload adv > $O/bench_line_adv.json 2>> $O/bench.err
+$B --full --workload adv --planner hardcode > $O/bench_line_adv_hardcode.json 2>> $O/bench.err
+$B --full --scenes 1 --agents 8 --steps 20 > $O/bench_line_1x8.json 2>> $O/bench.err
+$B --full --workload train --steps 10 --warmup 3 > $O/bench_line_train.json 2>> $O/bench.err
+$B --full --workload sample --steps 5 > $O/bench_line_sample.json 2>> $O/bench.err
+$B --full --workload sharded4096 --steps 5 > $O/bench_line_sharded4096_1gpu.json 2>> $O/bench.err
 timeout 400 rocprofv3 --kernel-trace --stats -d $O/ktt -- $B --workload train --steps 3 --warmup 1 > $O/ktt.log 2>&1
 DB=$(find $O/ktt -name "*.db" | head -1)
 python profiles/summarize_rocpd.py $DB | head -60 > $O/train_kernel_stats.txt 2>&1

@@ -8,9 +8,9 @@ rm -rf $O; mkdir -p $O
 B="python bench.py --no-cpu-baseline"
 for rep in 1 2; do
   cp strive_amd/libstrive_hip_conv1old.so strive_amd/libstrive_hip.so
-  $B > $O/bench_old_$rep.json 2>> $O/bench.err
+  $B --full > $O/bench_old_$rep.json 2>> $O/bench.err
   cp strive_amd/libstrive_hip_conv1new.so strive_amd/libstrive_hip.so
-  $B > $O/bench_new_$rep.json 2>> $O/bench.err
+  $B --full > $O/bench_new_$rep.json 2>> $O/bench.err
 done
 python tools/conv1_probe.py 512 > $O/conv1_probe_new.txt 2>&1
 timeout 300 python tools/cnn_stress.py > $O/cnn_stress.log 2>&1

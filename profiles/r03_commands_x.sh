@@ -7,8 +7,8 @@ rm -rf $O; mkdir -p $O
 B="python bench.py --no-cpu-baseline"
 for rep in 1 2; do
   cp strive_amd/libstrive_hip_old.so strive_amd/libstrive_hip.so
-  $B > $O/bench_old_$rep.json 2>> $O/bench.err
+  $B --full > $O/bench_old_$rep.json 2>> $O/bench.err
   cp strive_amd/libstrive_hip_new.so strive_amd/libstrive_hip.so
-  $B > $O/bench_new_$rep.json 2>> $O/bench.err
+  $B --full > $O/bench_new_$rep.json 2>> $O/bench.err
 done
 (timeout 900 python -m pytest tests/test_gpu_parity.py -m gpu -q 2>&1 | tail -3) > $O/tests_new.log

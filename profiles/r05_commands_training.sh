@@ -3,8 +3,8 @@
 cd $GRAFT_REPO_ROOT; export TMPDIR=/tmp
 O=gpurun_out/r05t_final; rm -rf $O; mkdir -p $O
 B="python bench.py --no-cpu-baseline --no-roofline"
-python bench.py > $O/bench_line_driver_default.json 2> $O/bench.err                                     # the driver's command
-python bench.py --no-cpu-baseline --workload train --steps 20 --warmup 4 > $O/bench_line_train.json 2>> $O/bench.err      # (with its roofline record)
+python bench.py --full > $O/bench_line_driver_default.json 2> $O/bench.err                                     # the driver's command
+python bench.py --full --no-cpu-baseline --workload train --steps 20 --warmup 4 > $O/bench_line_train.json 2>> $O/bench.err      # (with its roofline record)
 timeout 400 rocprofv3 --kernel-trace --stats -d $O/ktt -- $B --workload train --steps 6 --warmup 3 > $O/ktt.log 2>&1 < /dev/null
 DB=$(find $O/ktt -name "*.db" | head -1)
 python profiles/summarize_rocpd.py $DB | head -70 > $O/train_kernel_stats.txt 2>&1

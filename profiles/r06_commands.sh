@@ -26,15 +26,15 @@ python profiles/make_util.py $O/pmc_lds.txt $O/pmc_lds2.txt > $O/util.json 2>> $
 find $O -type f -size +1M -delete
 if [ -s $O/traffic.json ]; then cp $O/traffic.json profiles/r06_traffic.json; fi          # (this run's own counters feed bench.py's `traffic` / `on_chip_roofs` fields below)
 if [ -s $O/util.json ]; then cp $O/util.json profiles/r06_util.json; fi
-python bench.py --steps 20 --warmup 5 > $O/bench_line.json 2> $O/bench.err
-$B --workload adv --steps 20 --warmup 4 > $O/bench_line_adv.json 2>> $O/bench.err < /dev/null
-$B --workload adv --planner hardcode --steps 200 --warmup 4 > $O/bench_line_adv_hardcode.json 2>> $O/bench.err < /dev/null
-$B --scenes 1 --agents 8 --steps 40 --warmup 5 > $O/bench_line_1x8.json 2>> $O/bench.err < /dev/null
-$B --workload adv --planner hardcode --total-agents 8 --scenes 1 --steps 20 --warmup 6 > $O/bench_line_closed_loop_1x8.json 2>> $O/bench.err < /dev/null
-python bench.py --no-cpu-baseline --workload train --steps 10 --warmup 3 > $O/bench_line_train.json 2>> $O/bench.err      # (with its roofline record)
-$B --workload sample --steps 5 > $O/bench_line_sample.json 2>> $O/bench.err < /dev/null
-$B --workload sharded4096 --steps 5 > $O/bench_line_sharded4096_1gpu.json 2>> $O/bench.err < /dev/null
-$B --workload full --steps 1 --warmup 0 > $O/bench_line_full_pipeline.json 2>> $O/bench.err < /dev/null
+python bench.py --full --steps 20 --warmup 5 > $O/bench_line.json 2> $O/bench.err
+$B --full --workload adv --steps 20 --warmup 4 > $O/bench_line_adv.json 2>> $O/bench.err < /dev/null
+$B --full --workload adv --planner hardcode --steps 200 --warmup 4 > $O/bench_line_adv_hardcode.json 2>> $O/bench.err < /dev/null
+$B --full --scenes 1 --agents 8 --steps 40 --warmup 5 > $O/bench_line_1x8.json 2>> $O/bench.err < /dev/null
+$B --full --workload adv --planner hardcode --total-agents 8 --scenes 1 --steps 20 --warmup 6 > $O/bench_line_closed_loop_1x8.json 2>> $O/bench.err < /dev/null
+python bench.py --full --no-cpu-baseline --workload train --steps 10 --warmup 3 > $O/bench_line_train.json 2>> $O/bench.err      # (with its roofline record)
+$B --full --workload sample --steps 5 > $O/bench_line_sample.json 2>> $O/bench.err < /dev/null
+$B --full --workload sharded4096 --steps 5 > $O/bench_line_sharded4096_1gpu.json 2>> $O/bench.err < /dev/null
+$B --full --workload full --steps 1 --warmup 0 > $O/bench_line_full_pipeline.json 2>> $O/bench.err < /dev/null
 timeout 300 rocprofv3 --kernel-trace --stats -d $O/kt8 -- env STRIVE_HIP_GRAPH=0 $B --scenes 1 --agents 8 --steps 20 --warmup 3 > $O/kt8.log 2>&1 < /dev/null
 python profiles/summarize_rocpd.py $(find $O/kt8 -name "*.db" | head -1) | head -60 > $O/1x8_kernel_stats.txt 2>&1
 timeout 300 rocprofv3 --kernel-trace --stats -d $O/kta -- $B --workload adv --steps 5 --warmup 2 > $O/kta.log 2>&1 < /dev/null

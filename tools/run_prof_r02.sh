@@ -20,8 +20,8 @@ python profiles/summarize_pmc.py $(find $O/sq2 -name "*counter_collection.csv" |
 python profiles/make_traffic.py $O/pmc_fetch_size.txt $O/pmc_write_size.txt $O/kernel_stats.txt > $O/traffic.json 2>> $O/fetch.log
 find $O -type f -size +1M -delete
 cp $O/traffic.json profiles/r02_traffic.json          # (this run's own counters feed bench.py's `traffic` fields below)
-python bench.py > $O/bench_line.json 2> $O/bench.err
-python bench.py --workload adv --no-cpu-baseline > $O/bench_line_adv.json 2>> $O/bench.err
-python bench.py --scenes 1 --agents 8 --steps 20 --no-cpu-baseline > $O/bench_line_1x8.json 2>> $O/bench.err
-python bench.py --workload train --no-cpu-baseline --no-roofline > $O/bench_line_train.json 2>> $O/bench.err
+python bench.py --full > $O/bench_line.json 2> $O/bench.err
+python bench.py --full --workload adv --no-cpu-baseline > $O/bench_line_adv.json 2>> $O/bench.err
+python bench.py --full --scenes 1 --agents 8 --steps 20 --no-cpu-baseline > $O/bench_line_1x8.json 2>> $O/bench.err
+python bench.py --full --workload train --no-cpu-baseline --no-roofline > $O/bench_line_train.json 2>> $O/bench.err
 tail -c 300 $O/bench_line.json
