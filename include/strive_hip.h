@@ -196,7 +196,12 @@ typedef struct StriveScenes {
     const int32_t* scene_of;  /* (NA)  */
 } StriveScenes;
 
-/* Everything the decoder rollout needs besides per-call tensors. */
+/* Everything the decoder rollout needs besides per-call tensors.
+ * The width of decoder_net's last layer (gnn.mlp_out.dims[3]) selects the output model: 2 = (acceleration, yaw rate) through the
+ * kinematic bicycle model (output_bicycle=True); 4 = each step's local pose (x, y, hx, hy) in the frame of the previous global
+ * pose, heading normalised (output_bicycle=False, reference src/models/traffic_model.py:655-682).  With 4 outputs the bicycle
+ * fields (a_mean .. max_s) are ignored and scene_par may be NULL (it is not used: direct-output rollouts run on the
+ * launch-per-phase kernels). */
 typedef struct StriveDecoder {
     StriveGNN gnn;
     StriveGRU gru;
@@ -204,8 +209,8 @@ typedef struct StriveDecoder {
     StriveMap map;
     float state_mean[6], state_std[6];   /* (x,y,hx,hy,s,hdot) normaliser, datasets/utils.py:44-113 */
     float att_mean[2], att_std[2];       /* (l,w) normaliser */
-    float a_mean, a_std, ddh_mean, ddh_std, dt, max_hdot, max_s;   /* NUSC_BIKE_PARAMS, datasets/utils.py:121-127 */
-    /* optional (ABI 14; NULL = the scene-resident kernels are not used): the small parameters of decoder_net / decoder_memory in
+    float a_mean, a_std, ddh_mean, ddh_std, dt, max_hdot, max_s;   /* NUSC_BIKE_PARAMS, datasets/utils.py:121-127 (bicycle only) */
+    /* optional (ABI 14; NULL = the scene-resident kernels are not used; laid out for a 2-output decoder only): the small parameters of decoder_net / decoder_memory in
      * one block of 6340 floats that those kernels copy to LDS -- offsets in floats (csrc/scene_rollout.h Par):
      * mlp_in  b0 0, b1 128, b2 256, ln_g0 320, ln_b0 448, ln_g1 576, ln_b1 704;
      * edge    b0 832, b1 960, b2 1088, ln_g0 1152, ln_b0 1280, ln_g1 1408, ln_b1 1536, W_rel^T (4,128) = rows 128+2NC.. of wt[0] 1664;
@@ -312,13 +317,16 @@ size_t strive_rollout_workspace_bytes(const StriveDecoder* dec, const StriveScen
  * launch-per-phase kernels.  Same arithmetic scheme, same tape layout; results agree to fp32 rounding.  Option
  * scene_kernels = 0 (read per call) forces 0.  2 (round 6): a single-sample batch with scenes of more than 16 agents -- the node-level
  * phases of the forward step (mlp_in .. edge partials; update MLP .. GRU .. dynamics) run on the scene kernel in 16-row tiles of
- * every scene, the edge rows and the reverse sweep on the launch-per-phase kernels (option scene_tiles = 0: all per-phase). */
+ * every scene, the edge rows and the reverse sweep on the launch-per-phase kernels (option scene_tiles = 0: all per-phase).
+ * Always 0 for a direct-output decoder (4 outputs): its rollouts run on the launch-per-phase kernels at every scene size. */
 int strive_rollout_scene_resident(const StriveDecoder* dec, const StriveScenes* sc);
 
 /* TrafficModel.autoregressive_decoder (reference src/models/traffic_model.py:589-704).
  * past_last (NA,6) normalised last past state; lw (NA,2) normalised; sem (NA,NC); past_feat, map_feat
  * (NA,64); z (R,32); mapix (NA); ext_future (B,FT,4) normalised or NULL (ego rows teacher-forced,
- * lines 667-675).  traj (R,FT,4): normalised global (x,y,hx,hy).  tape keeps what the backward needs. */
+ * lines 667-675).  traj (R,FT,4): normalised global (x,y,hx,hy).  tape keeps what the backward needs.
+ * Direct-output decoder (4 outputs): only past_last[:, :4] is read; a teacher-forced ego row's given pose also becomes its
+ * previous pose of the next step (lines 679-682), and traj holds the predicted pose before that replacement. */
 int strive_rollout_fwd(const StriveDecoder* dec, const StriveScenes* sc, const float* past_last,
                        const float* lw, const float* sem, const float* past_feat, const float* map_feat,
                        const float* z, const int32_t* mapix, const float* ext_future, int32_t FT,
@@ -326,7 +334,7 @@ int strive_rollout_fwd(const StriveDecoder* dec, const StriveScenes* sc, const f
                        strive_stream_t stream);
 
 /* d(loss)/dz given d(loss)/d(traj): the reverse-time sweep of SURVEY.md Appendix A (no gradient flows
- * through the map crop / CNN: the reference crops at pos.detach(), traffic_model.py:694). */
+ * through the map crop / CNN: the reference crops at pos.detach(), traffic_model.py:694).  Both output models (StriveDecoder). */
 int strive_rollout_bwd(const StriveDecoder* dec, const StriveScenes* sc, const float* lw, const float* sem,
                        const float* z, const float* ext_future, int32_t FT, const float* d_traj,
                        float* dz, const void* tape, size_t tape_bytes, void* ws, size_t ws_bytes,
@@ -548,7 +556,8 @@ int strive_rollout_bwd_train_kept(const StriveDecoder* dec, const StriveScenes* 
 /* autoregressive_decoder under autograd with parameter gradients (reference src/models/traffic_model.py:589-704 as used
  * by forward(), :178-225): like strive_rollout_bwd, plus d_past_feat, d_map_feat (NA,64) -- the adjoints of the encoder
  * outputs the rollout starts from -- and the gradients of decoder_net (d_gnn), decoder_memory (d_gru) and of the map CNN
- * (d_cnn: every step t >= 1 re-encodes the map at the detached pose, :694-695), all (+=).  NS must be 1. */
+ * (d_cnn: every step t >= 1 re-encodes the map at the detached pose, :694-695), all (+=).  NS must be 1.  Both output models
+ * (StriveDecoder): d_gnn's last mlp_out layer is (2,128) + 2 or (4,128) + 4. */
 int strive_rollout_bwd_train(const StriveDecoder* dec, const StriveScenes* sc, const float* lw, const float* sem,
                              const float* z, const float* ext_future, const int32_t* mapix, int32_t FT, const float* d_traj,
                              float* dz, float* d_past_feat, float* d_map_feat, float* d_gnn, float* d_gru, float* d_cnn,

@@ -182,6 +182,52 @@ __device__ __forceinline__ void bike_backward(const DynParams& p, const BikeFwd&
 }
 
 // ---------------------------------------------------------------------------------------------
+// direct output step on one row (output_bicycle=False; reference src/models/traffic_model.py:655-662,
+// src/utils/transforms.py:78-139 inverse branch): the decoder's 4 outputs are the local pose in the frame of the previous
+// global pose, heading normalised to a unit vector.  All values normalised; no epsilon (a zero heading gives NaN, as there).
+// ---------------------------------------------------------------------------------------------
+struct DirectFwd {
+    float n;            // |heading| of the decoder output
+    float loc[4];       // local pose (x, y, hx / n, hy / n)
+    float out[4];       // global pose
+};
+
+__device__ __forceinline__ void direct_forward(const float* prev, const float* dec, DirectFwd& d) {
+    d.n = sqrtf(dec[2] * dec[2] + dec[3] * dec[3]);
+    d.loc[0] = dec[0];
+    d.loc[1] = dec[1];
+    d.loc[2] = dec[2] / d.n;
+    d.loc[3] = dec[3] / d.n;
+    const float c = prev[2], s = prev[3];
+    d.out[0] = (c * d.loc[0] - s * d.loc[1]) + prev[0];
+    d.out[1] = (s * d.loc[0] + c * d.loc[1]) + prev[1];
+    d.out[2] = d.loc[2] * c - d.loc[3] * s;
+    d.out[3] = d.loc[3] * c + d.loc[2] * s;
+}
+
+// adjoint: gout (4, w.r.t. the global pose) and gloc (4, w.r.t. the local pose where it is used directly: the GRU input) ->
+// gprev (4, accumulated: w.r.t. the previous global pose), gdec (4, w.r.t. the decoder output)
+__device__ __forceinline__ void direct_backward(const float* prev, const DirectFwd& d, const float* gout, const float* gloc,
+                                                float* gprev, float* gdec) {
+    const float c = prev[2], s = prev[3];
+    const float g0 = gout[0], g1 = gout[1], g2 = gout[2], g3 = gout[3];
+    const float gl0 = gloc[0] + c * g0 + s * g1;
+    const float gl1 = gloc[1] - s * g0 + c * g1;
+    const float gl2 = gloc[2] + c * g2 + s * g3;
+    const float gl3 = gloc[3] - s * g2 + c * g3;
+    gprev[0] += g0;
+    gprev[1] += g1;
+    gprev[2] += g0 * d.loc[0] + g1 * d.loc[1] + g2 * d.loc[2] + g3 * d.loc[3];
+    gprev[3] += g1 * d.loc[0] - g0 * d.loc[1] + g3 * d.loc[2] - g2 * d.loc[3];
+    // u = h / |h|:  du/dh = (I - u u^T) / |h|
+    const float dot = d.loc[2] * gl2 + d.loc[3] * gl3;
+    gdec[0] = gl0;
+    gdec[1] = gl1;
+    gdec[2] = (gl2 - d.loc[2] * dot) / d.n;
+    gdec[3] = (gl3 - d.loc[3] * dot) / d.n;
+}
+
+// ---------------------------------------------------------------------------------------------
 // GRU helpers (one time step, 3 layers, hidden 64; torch.nn.GRU gate order r,z,n)
 // ---------------------------------------------------------------------------------------------
 #define GLD 192
@@ -235,6 +281,9 @@ struct StepArgs {
     float* traj;               // (R, FT, 4)
 };
 
+// DIRECT: the decoder's 4 outputs are the local pose (direct_forward); state_t then holds the 4-d global pose, which for a
+// forced ego row (ext_future) is the given pose (reference traffic_model.py:667-682)
+template <bool DIRECT>
 static __global__ __launch_bounds__(256) void rollout_node2_kernel(GNNDev g, GRUDev gru, DynParams dp, StepArgs a, Tape tp) {
     HIP_DYNAMIC_SHARED(float, smem)
     const int in_ld = ld4(2 * g.D + g.NC);
@@ -261,7 +310,35 @@ static __global__ __launch_bounds__(256) void rollout_node2_kernel(GNNDev g, GRU
     if (tid < RB_NODE) {
         const int r = r0 + tid;
         float loc[4] = {0.f, 0.f, 0.f, 0.f};
-        if (r < a.R) {
+        if (DIRECT && r < a.R) {
+            const int ag = r / a.NS;
+            const float* st = tp.state_t(t) + (size_t)r * 8;
+            const float dec[4] = {L.out[tid * HLD + 0], L.out[tid * HLD + 1], L.out[tid * HLD + 2], L.out[tid * HLD + 3]};
+            DirectFwd d;
+            direct_forward(st, dec, d);
+            for (int i = 0; i < 4; ++i) tp.DEC_t(t)[(size_t)r * 4 + i] = dec[i];
+            float* tr = a.traj + ((size_t)r * a.FT + t) * 4;
+            for (int i = 0; i < 4; ++i) tr[i] = d.out[i];
+            // GRU input: the normalised decoder output itself, or the given pose in the previous frame for a forced ego row
+            float gin[4] = {d.out[0], d.out[1], d.out[2], d.out[3]};
+            for (int i = 0; i < 4; ++i) loc[i] = d.loc[i];
+            if (a.ext) {
+                const int sc = a.scene_of[ag];
+                if (a.ptr[sc] == ag) {
+                    const float* e = a.ext + ((size_t)sc * a.FT + t) * 4;
+                    for (int i = 0; i < 4; ++i) gin[i] = e[i];
+                    rel_pose(st, gin, loc);
+                }
+            }
+            float* lo = tp.loc_t(t) + (size_t)r * 4;
+            for (int i = 0; i < 4; ++i) lo[i] = loc[i];
+            if (more) {
+                float* ns = tp.state_t(t + 1) + (size_t)r * 8;
+                for (int i = 0; i < 4; ++i) ns[i] = gin[i];
+                float* np = tp.pos_t(t + 1) + (size_t)r * 4;
+                for (int i = 0; i < 4; ++i) np[i] = gin[i];
+            }
+        } else if (!DIRECT && r < a.R) {
             const int ag = r / a.NS;
             const float* st = tp.state_t(t) + (size_t)r * 8;
             BikeFwd b;
@@ -337,6 +414,9 @@ static __global__ void rollout_init_kernel(Tape tp, const float* __restrict__ pa
     if (c < 4) tp.pos_t(0)[(size_t)r * 4 + c] = past_last[(size_t)ag * 6 + c];
     if (c == 0) mapix_rows[r] = mapix[ag];
 }
+
+// 4 decoder outputs = the direct pose output (output_bicycle=False), 2 = (acceleration, yaw rate) into the bicycle model
+static inline bool decoder_direct(const StriveDecoder& d) { return d.gnn.mlp_out.dims[3] == 4; }
 
 #include "scene_rollout.h"
 
@@ -434,7 +514,10 @@ size_t node2r_lds_bytes(int in_ld) { return (Node2Lds::floats(in_ld) + RB_NODE *
 
 int check_decoder(const StriveDecoder* dec, const StriveScenes* sc, int FT) {
     if (gnn_check(dec->gnn)) return -1;
-    if (dec->gnn.D != 64 || dec->gnn.mlp_out.dims[3] != 2) { strive_set_error("rollout: decoder_net must have D=64 and 2 outputs"); return -1; }
+    if (dec->gnn.D != 64 || (dec->gnn.mlp_out.dims[3] != 2 && dec->gnn.mlp_out.dims[3] != 4)) {
+        strive_set_error("rollout: decoder_net must have D=64 and 2 (bicycle) or 4 (direct pose) outputs");
+        return -1;
+    }
     if (dec->gnn.mlp_in.dims[0] != 64 + 64 + dec->gnn.NC + STRIVE_ZDIM + 2) { strive_set_error("rollout: decoder_net input width mismatch"); return -1; }
     if (FT < 1 || sc->NA < 0 || sc->NS < 1) { strive_set_error("rollout: bad sizes"); return -1; }
     return 0;
@@ -497,6 +580,7 @@ static int rollout_forward(const StriveDecoder* dec, const StriveScenes* sc, con
     const int in_ld1 = ld4(dec->gnn.mlp_in.dims[0]), xs_ld = ld4(64 + NC), in_ld2 = ld4(128 + NC);
     const int nb = (int)((R + RB_NODE - 1) / RB_NODE);
 
+    const bool direct = decoder_direct(*dec);
     const bool scene = scene_kernels_on(dec, sc);
     const bool scene_tiles = !scene && scene_tiles_on(dec, sc);
     if ((scene || scene_tiles) && scene_kernels_prepare()) return -1;
@@ -600,7 +684,10 @@ static int rollout_forward(const StriveDecoder* dec, const StriveScenes* sc, con
         StepArgs a;
         a.t = t; a.FT = FT; a.R = (int)R; a.NS = sc->NS; a.X = gb.X; a.sem = sem; a.lw = lw; a.ext = ext_future;
         a.ptr = sc->ptr; a.scene_of = sc->scene_of; a.traj = traj;
-        hipLaunchKernelGGL(rollout_node2_kernel, dim3(nb), dim3(256), node2r_lds_bytes(in_ld2), stream, gd, gr, dp, a, tp);
+        if (direct)
+            hipLaunchKernelGGL(rollout_node2_kernel<true>, dim3(nb), dim3(256), node2r_lds_bytes(in_ld2), stream, gd, gr, dp, a, tp);
+        else
+            hipLaunchKernelGGL(rollout_node2_kernel<false>, dim3(nb), dim3(256), node2r_lds_bytes(in_ld2), stream, gd, gr, dp, a, tp);
         if (t < FT - 1) {
             int rc = encode_step(t);
             if (rc) return rc;
@@ -749,12 +836,13 @@ struct Node2BwdArgs {
     float* dA;               // (R, 64) out: dL/d(aggregated message)
 };
 
-template <bool WG>
+// DIRECT: the 4-output decoder of rollout_node2_kernel<true>
+template <bool WG, bool DIRECT>
 static __global__ __launch_bounds__(256) void node2_bwd_kernel(GNNDev g, GNNGradDev gr, DynParams dp, Node2BwdArgs a, Tape tp) {
     HIP_DYNAMIC_SHARED(float, smem)
     const int in_ld = ld4(2 * g.D + g.NC);
     Node2Lds L(smem, in_ld);
-    float* s_go = L.out + RB_NODE * HLD;      // [RB_NODE][4]  gradient w.r.t. decoder output (2 used)
+    float* s_go = L.out + RB_NODE * HLD;      // [RB_NODE][4]  gradient w.r.t. decoder output (2 used by the bicycle model)
     float* s_ga = s_go + RB_NODE * 4;         // [RB_NODE][HLD]
     float* s_gb = s_ga + RB_NODE * HLD;       // [RB_NODE][HLD]
     float* s_gx = s_gb + RB_NODE * HLD;       // [RB_NODE][HLD] gradient w.r.t. x'
@@ -771,7 +859,12 @@ static __global__ __launch_bounds__(256) void node2_bwd_kernel(GNNDev g, GNNGrad
                 L.pre_o[(size_t)l * RB_NODE * HLD + rr * HLD + c] = live ? tp.PRE_O_t(t)[(size_t)(r0 + rr) * 2 * STRIVE_HID + q] : 0.f;
             }
         }
-        if (tid < RB_NODE * 2) {
+        if (DIRECT) {
+            if (tid < RB_NODE * 4) {
+                const int rr = tid >> 2, c = tid & 3;
+                L.out[rr * HLD + c] = (r0 + rr < a.R) ? tp.DEC_t(t)[(size_t)(r0 + rr) * 4 + c] : 0.f;
+            }
+        } else if (tid < RB_NODE * 2) {
             const int rr = tid >> 1, c = tid & 1;
             L.out[rr * HLD + c] = (r0 + rr < a.R) ? tp.DEC_t(t)[(size_t)(r0 + rr) * 4 + c] : 0.f;
         }
@@ -796,7 +889,44 @@ static __global__ __launch_bounds__(256) void node2_bwd_kernel(GNNDev g, GNNGrad
         if (WG) mlp_forward_lds<RB_NODE>(g.update, L.in, in_ld, L.pre_u, L.act, L.xp, HLD, /*first_done=*/true, tid, 256);
     }
     const bool more = t < a.FT - 1;
-    if (tid < RB_NODE) {
+    if (DIRECT && tid < RB_NODE) {
+        const int r = r0 + tid;
+        float gdec[4] = {0.f, 0.f, 0.f, 0.f};
+        if (r < a.R) {
+            const int ag = r / a.NS;
+            const float* st = tp.state_t(t) + (size_t)r * 8;
+            const float dec[4] = {L.out[tid * HLD + 0], L.out[tid * HLD + 1], L.out[tid * HLD + 2], L.out[tid * HLD + 3]};
+            DirectFwd d;
+            direct_forward(st, dec, d);
+            const float* ext = nullptr;
+            if (a.ext) {
+                const int sc = a.scene_of[ag];
+                if (a.ptr[sc] == ag) ext = a.ext + ((size_t)sc * a.FT + t) * 4;
+            }
+            float gglob[4], gloc[4] = {0.f, 0.f, 0.f, 0.f}, gprev[4] = {0.f, 0.f, 0.f, 0.f};
+            const float* gt = a.g_traj + ((size_t)r * a.FT + t) * 4;
+            for (int i = 0; i < 4; ++i) gglob[i] = gt[i];
+            if (more) {
+                const float* dl = a.d_loc + (size_t)r * 4;
+                if (ext) {
+                    // the next state, pose and GRU input come from the given pose: only the GRU input's frame is differentiable
+                    float gpo[4] = {0.f, 0.f, 0.f, 0.f};
+                    rel_pose_bwd(st, ext, dl, gprev, gpo);
+                } else {
+                    const float* gs = a.g_state + (size_t)r * 8;
+                    for (int i = 0; i < 4; ++i) {
+                        gglob[i] += gs[i] + a.g_pos[(size_t)r * 4 + i];
+                        gloc[i] = dl[i];
+                    }
+                }
+            }
+            direct_backward(st, d, gglob, gloc, gprev, gdec);
+            float* go = a.g_state + (size_t)r * 8;
+            for (int i = 0; i < 4; ++i) go[i] = gprev[i];
+            go[4] = go[5] = 0.f;
+        }
+        for (int i = 0; i < 4; ++i) s_go[tid * 4 + i] = gdec[i];
+    } else if (!DIRECT && tid < RB_NODE) {
         const int r = r0 + tid;
         float gdec[2] = {0.f, 0.f};
         if (r < a.R) {
@@ -1019,6 +1149,7 @@ int rollout_backward(const StriveDecoder* dec, const StriveScenes* sc, const flo
     const int NC = dec->gnn.NC;
     const int in_ld1 = ld4(dec->gnn.mlp_in.dims[0]), xs_ld = ld4(64 + NC), in_ld2 = ld4(128 + NC);
     const int nb = (int)((R + RB_NODE - 1) / RB_NODE);
+    const bool direct = decoder_direct(*dec);
 
     // Training, kept activations: the map CNN's backward of the crops of step t needs nothing but the map-feature adjoints node1_bwd(t)
     // leaves -- and the sweep is a chain of small kernels on <= R workgroups while the CNN backward fills the chip.  The crops of
@@ -1065,7 +1196,10 @@ int rollout_backward(const StriveDecoder* dec, const StriveScenes* sc, const flo
         a2.t = t; a2.FT = FT; a2.R = (int)R; a2.NS = sc->NS; a2.X = g2.X; a2.sem = sem; a2.lw = lw; a2.ext = ext_future;
         a2.ptr = sc->ptr; a2.scene_of = sc->scene_of; a2.g_traj = d_traj; a2.g_pos = g_pos; a2.d_loc = d_loc;
         a2.g_state = g_state; a2.dX = bw.dX; a2.dA = bw.dA;
-        hipLaunchKernelGGL(node2_bwd_kernel<WG>, dim3(nb), dim3(256), node2_bwd_lds_bytes(in_ld2), stream, gd, ggn, dp, a2, tp);
+        if (direct)
+            hipLaunchKernelGGL((node2_bwd_kernel<WG, true>), dim3(nb), dim3(256), node2_bwd_lds_bytes(in_ld2), stream, gd, ggn, dp, a2, tp);
+        else
+            hipLaunchKernelGGL((node2_bwd_kernel<WG, false>), dim3(nb), dim3(256), node2_bwd_lds_bytes(in_ld2), stream, gd, ggn, dp, a2, tp);
         EdgeBwdArgs ae;
         ae.dA = bw.dA; ae.ARG = tp.ARG_t(t); ae.dP = bw.dP; ae.DE1 = bw.DE1; ae.DPJ = bw.DPJ; ae.gpos_tgt = bw.gpos_tgt;
         hipLaunchKernelGGL(edge_bwd_kernel<WG>, dim3((unsigned)R), dim3(256), edge_bwd_lds_bytes(), stream, gd, ggn, sd, tp.pos_t(t),

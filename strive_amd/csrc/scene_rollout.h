@@ -69,6 +69,7 @@ static inline GRUFrag gru_frag(const StriveGRU& g) {
 static inline bool supported(const StriveDecoder& d, const StriveScenes& sc, bool any_size = false) {
     if (sc.NS != 1 || (sc.max_n > NR && !any_size) || sc.max_n < 1 || !d.scene_par) return false;
     if (d.gnn.D != 64 || d.gnn.NC > 8) return false;
+    if (d.gnn.mlp_out.dims[3] != 2) return false;        // the bicycle head only (Par packs a 2-wide mlp_out; direct output: rollout.hip)
     // k-step counts the kernels are written for: mlp_in 162 + NC -> 6, edge layer 0 (132 + 2 NC: sem_i, sem_j and the relative
     // pose share the 5th step), update 128 + NC -> 5
     if (((d.gnn.mlp_in.dims[0] + 31) >> 5) != 6 || ((d.gnn.edge.dims[0] + 31) >> 5) != 5 || ((d.gnn.update.dims[0] + 31) >> 5) != 5) return false;

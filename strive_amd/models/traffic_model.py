@@ -10,8 +10,12 @@ enqueues the whole FT-step kernel sequence, and its backward is an explicit reve
 yields d/dz only when the loops call ``decode_embedding`` (what the latent optimisation needs, SURVEY.md
 Appendix A) and, inside ``forward()`` (training), also the gradients of every parameter.
 
-Not supported (raise NotImplementedError): ``traj_encoder='gru'``, ``output_bicycle=False`` and
-non-default map-CNN shapes -- no shipped config uses them (last paragraph).
+Both output parameterisations of the reference are served: ``output_bicycle=True`` (the decoder's 2 outputs, acceleration
+and yaw rate, go through the kinematic bicycle model; ``set_bicycle_params`` must be called) and ``output_bicycle=False``
+(``--no_output_bicycle``: the decoder's 4 outputs are each step's local pose, no bicycle parameters).
+
+Not supported (raise NotImplementedError): ``traj_encoder='gru'`` and non-default map-CNN shapes -- no shipped config uses
+them (last paragraph).
 """
 import os
 
@@ -40,8 +44,6 @@ class TrafficModel(nn.Module):
         super(TrafficModel, self).__init__()
         if traj_encoder != 'mlp':
             raise NotImplementedError("strive_amd implements traj_encoder='mlp' (the only one shipped configs use)")
-        if not output_bicycle:
-            raise NotImplementedError('strive_amd implements the bicycle output parameterisation only')
         if (list(conv_kernel_list), list(conv_stride_list), list(conv_filter_list), conv_channel_in, map_obs_size_pix) != \
                 ([7, 5, 5, 3, 3, 3], [2] * 6, [16, 32, 64, 64, 128, 128], 4, 256):
             raise NotImplementedError('strive_amd implements the default map CNN (4x256x256 crop, 6 stride-2 convs) only')
@@ -50,7 +52,7 @@ class TrafficModel(nn.Module):
         self.normalizer = self.att_normalizer = None
         self.PT, self.FT, self.NC = npast, nfuture, nclasses
         self.dt = 0.5
-        self.output_bicycle = True
+        self.output_bicycle = bool(output_bicycle)
         self.bicycle_params = None
         # forward(future_sample=True): both decodes as one rollout over the batch stacked twice (STRIVE_STACK_ROLLOUTS=0: one after
         # the other, the round-4 form)
@@ -84,7 +86,8 @@ class TrafficModel(nn.Module):
                                              2 * past_feat_size, 2 * latent_size)
         self.posterior_net = SceneInteractionNet(future_feat_size + past_feat_size + map_feat_size + self.NC, self.NC, 4,
                                                  2 * past_feat_size, 2 * latent_size)
-        self.traj_out_size = 2
+        # (a, hdot) for the bicycle model, (x, y, hx, hy) in the frame of the previous step otherwise (reference :139-142)
+        self.traj_out_size = 2 if self.output_bicycle else 4
         self.decoder_net = SceneInteractionNet(latent_size + past_feat_size + map_feat_size + self.NC + self.att_feat_size,
                                                self.NC, 4, 64, self.traj_out_size)
         self.num_memory_layers = 3

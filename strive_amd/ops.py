@@ -856,10 +856,12 @@ def _decoder_variant(pack):
 def _decoder_pack_key(model, map_env, dev):
     key = ('dec', str(dev), map_env.nusc_raster.data_ptr())
     # plain values the pack copies: normaliser statistics and the bicycle parameters (not object identities)
-    nm, an, bp = model.normalizer, model.att_normalizer, model.bicycle_params
+    # (a direct-output model -- output_bicycle=False -- has none; the output mode is part of the key)
+    nm, an = model.normalizer, model.att_normalizer
+    bp = model.bicycle_params if model.output_bicycle else {}
     extra = (tuple(nm.mean_vals.tolist()), tuple(nm.std_vals.tolist()), tuple(an.mean_vals.tolist()), tuple(an.std_vals.tolist()),
              tuple(sorted((k, tuple(v) if isinstance(v, (tuple, list)) else v) for k, v in bp.items())),
-             tuple(map_env.bounds), map_env.L, map_env.W)
+             tuple(map_env.bounds), map_env.L, map_env.W, bool(model.output_bicycle))
     return key, extra
 
 
@@ -868,7 +870,7 @@ def decoder_packs_ready(model, g, map_env, NS, dev):
     descriptor and the map pack are cached.  Callers that fork side streams (utils.adv_gen_optim.two_rollouts) run serially
     on their own stream until this holds, so that packs are always built -- and their memory owned -- by the caller's stream
     and never written on one stream while another one reads them."""
-    if model.normalizer is None or model.att_normalizer is None or model.bicycle_params is None:
+    if model.normalizer is None or model.att_normalizer is None or (model.output_bicycle and model.bicycle_params is None):
         return False
     info = scene_info(g)                      # (host work + two small uploads on the caller's stream the first time)
     key, extra = _decoder_pack_key(model, map_env, dev)
@@ -929,8 +931,10 @@ def _rollout_context(model, g, map_feat, past_feat, z, map_idx, map_env, ext_fut
     """descriptors, per-call tensors and sizes of one rollout (shared by decoder_rollout and decoder_rollout_pair);
     ``copies`` > 1: of the batch stacked that many times (decoder_rollout_stacked)"""
     lib = _lib_for(z, map_feat, past_feat, g.past)
-    if model.normalizer is None or model.att_normalizer is None or model.bicycle_params is None:
-        raise RuntimeError('set_normalizer / set_att_normalizer / set_bicycle_params must be called before decoding')
+    if model.normalizer is None or model.att_normalizer is None:
+        raise RuntimeError('set_normalizer / set_att_normalizer must be called before decoding')
+    if model.output_bicycle and model.bicycle_params is None:
+        raise RuntimeError('set_bicycle_params must be called before decoding with the bicycle output model')
     if train:
         _no_grad_inputs('decoder (ext_future)', ext_future)
     else:
@@ -947,7 +951,8 @@ def _rollout_context(model, g, map_feat, past_feat, z, map_idx, map_env, ext_fut
 
     def build():
         return params.pack_decoder(model.state_dict(), NC, map_env, dev, model.normalizer, model.att_normalizer,
-                                   model.bicycle_params, cnn=cnn_pack(model), map_pack=_map_pack(map_env, dev))
+                                   model.bicycle_params if model.output_bicycle else None, cnn=cnn_pack(model),
+                                   map_pack=_map_pack(map_env, dev))
     key, extra = _decoder_pack_key(model, map_env, dev)
     h = _RolloutCtx()
     h.lib = lib

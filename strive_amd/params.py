@@ -513,7 +513,8 @@ def pack_map(map_env, device):
 
 
 def pack_decoder(sd, NC, map_env, device, state_norm, att_norm, bike, cnn=None, map_pack=None):
-    """state_norm / att_norm: objects with mean_vals/std_vals (MeanStdNormalizer API); bike: dict; ``cnn``: an up-to-date
+    """state_norm / att_norm: objects with mean_vals/std_vals (MeanStdNormalizer API); bike: dict, or None for a direct-output
+    decoder (4 outputs, output_bicycle=False); ``cnn``: an up-to-date
     pack_cnn() of the same parameters to share (its tensors are kept alive by the returned pack) instead of packing the map
     CNN a second time; ``map_pack``: likewise a pack_map() of (map_env, device) -- the training step rebuilds the decoder pack
     after every optimiser step, and building the map pack again (interleaved raster copy, two host-to-device table uploads)
@@ -538,12 +539,18 @@ def pack_decoder(sd, NC, map_env, device, state_norm, att_norm, bike, cnn=None, 
     for i in range(2):
         s.att_mean[i] = float(att_norm.mean_vals[i])
         s.att_std[i] = float(att_norm.std_vals[i])
-    s.a_mean, s.a_std = bike['a_stats']
-    s.ddh_mean, s.ddh_std = bike['ddh_stats']
-    s.dt = bike['dt']
-    s.max_hdot = bike['maxhdot']
-    s.max_s = bike['maxs']
-    s.scene_par = p.hold(_scene_par(sd, NC).to(device))
+    if bike is not None:
+        s.a_mean, s.a_std = bike['a_stats']
+        s.ddh_mean, s.ddh_std = bike['ddh_stats']
+        s.dt = bike['dt']
+        s.max_hdot = bike['maxhdot']
+        s.max_s = bike['maxs']
+    else:       # the direct-output model (output_bicycle=False) has no bicycle parameters: the library ignores these fields
+        s.a_mean = s.a_std = s.ddh_mean = s.ddh_std = s.dt = s.max_hdot = s.max_s = 0.0
+    # the scene-resident kernels' block lays out a 2-wide decoder head: a direct-output decoder (4 outputs) leaves it NULL and
+    # runs on the launch-per-phase kernels
+    if sd['decoder_net.mlp_out.net.6.weight'].shape[0] == 2:
+        s.scene_par = p.hold(_scene_par(sd, NC).to(device))
     return p
 
 
