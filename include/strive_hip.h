@@ -33,6 +33,9 @@ extern "C" {
 #define STRIVE_ABI_VERSION 17
 #define STRIVE_HID 128        /* hidden width of every MLP in the reference (models/common.py, interaction_net.py:32,41) */
 #define STRIVE_MAX_LAYERS 4
+/* Latent width Z of the shipped model (latent_size=32).  The library takes a decoder's Z from its pack:
+ * Z = gnn.mlp_in.dims[0] - (64 + 64 + NC + 2), any width from 1 to 64; every z / dz buffer of the rollout entry points has
+ * row stride Z. */
 #define STRIVE_ZDIM 32
 #define STRIVE_FEAT 64        /* map / past feature size and GRU hidden size (traffic_model.py:25-27) */
 
@@ -323,8 +326,8 @@ int strive_rollout_scene_resident(const StriveDecoder* dec, const StriveScenes* 
 
 /* TrafficModel.autoregressive_decoder (reference src/models/traffic_model.py:589-704).
  * past_last (NA,6) normalised last past state; lw (NA,2) normalised; sem (NA,NC); past_feat, map_feat
- * (NA,64); z (R,32); mapix (NA); ext_future (B,FT,4) normalised or NULL (ego rows teacher-forced,
- * lines 667-675).  traj (R,FT,4): normalised global (x,y,hx,hy).  tape keeps what the backward needs.
+ * (NA,64); z (R,Z) (Z: the decoder pack's latent width, see STRIVE_ZDIM); mapix (NA); ext_future (B,FT,4) normalised or
+ * NULL (ego rows teacher-forced, lines 667-675).  traj (R,FT,4): normalised global (x,y,hx,hy).  tape keeps what the backward needs.
  * Direct-output decoder (4 outputs): only past_last[:, :4] is read; a teacher-forced ego row's given pose also becomes its
  * previous pose of the next step (lines 679-682), and traj holds the predicted pose before that replacement. */
 int strive_rollout_fwd(const StriveDecoder* dec, const StriveScenes* sc, const float* past_last,

@@ -189,7 +189,7 @@ struct Node1BwdArgs {
     float* g_full;          // (R, F)  the whole feature row (stand-alone network)
     float* g_pf;            // (R, 64) columns [0, 64)      (rollout: past_feat_t)
     float* g_mf;            // (R, 64) columns [64, 128)    (rollout, training: map_feat_t)
-    float* dz;              // (R, 32) columns [128+NC, 128+NC+32), ACCUMULATED   (rollout: the latents)
+    float* dz;              // (R, Z) columns [128+NC, 128+NC+Z), Z = F - 130 - NC, ACCUMULATED   (rollout: the latents)
 };
 
 template <bool WG>
@@ -306,10 +306,11 @@ static __global__ __launch_bounds__(256) void node1_bwd_kernel(GNNDev g, GNNGrad
         }
     }
     if (a.dz) {
-        const int zoff = 128 + g.NC;
-        for (int i = tid; i < RB_NODE * STRIVE_ZDIM; i += 256) {
-            const int rr = i / STRIVE_ZDIM, c = i - rr * STRIVE_ZDIM;
-            if (r0 + rr < a.R) a.dz[(size_t)(r0 + rr) * STRIVE_ZDIM + c] += s_gin[rr * in_ld + zoff + c];
+        // the latent columns of the decoder's features: [past_feat 64 | map_feat 64 | sem NC | z Z | lw 2]
+        const int zoff = 128 + g.NC, Z = F - zoff - 2;
+        for (int i = tid; i < RB_NODE * Z; i += 256) {
+            const int rr = i / Z, c = i - rr * Z;
+            if (r0 + rr < a.R) a.dz[(size_t)(r0 + rr) * Z + c] += s_gin[rr * in_ld + zoff + c];
         }
     }
 }

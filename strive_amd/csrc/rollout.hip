@@ -11,6 +11,7 @@
 // at all because the reference crops at pos.detach()).  The backward is four launches per step:
 // node1 (recompute), gru_bwd, node2_bwd, edge_bwd, node1_bwd.
 #include <atomic>
+#include <type_traits>
 #include "gnn_bwd_kernels.h"
 
 struct DynParams {
@@ -418,7 +419,23 @@ static __global__ void rollout_init_kernel(Tape tp, const float* __restrict__ pa
 // 4 decoder outputs = the direct pose output (output_bicycle=False), 2 = (acceleration, yaw rate) into the bicycle model
 static inline bool decoder_direct(const StriveDecoder& d) { return d.gnn.mlp_out.dims[3] == 4; }
 
+// latent width Z: decoder_net's input is [past_feat 64 | map_feat 64 | sem NC | z Z | lw 2] (traffic_model.py:628-629); every z / dz
+// buffer of a rollout has row stride Z
+static inline int decoder_zdim(const StriveDecoder& d) { return d.gnn.mlp_in.dims[0] - (64 + 64 + d.gnn.NC + 2); }
+
 #include "scene_rollout.h"
+
+// The scene kernels' form for a decoder (scn::latent_width): fn(KIN, ZFIX) with both as std::integral_constant.  The shipped width
+// runs the form that has it compiled in; any other width (scn::supported: 1 .. 64) the one for its mlp_in k-step count.
+template <typename Fn>
+static inline void scene_form(const StriveDecoder& d, Fn&& fn) {
+    using std::integral_constant;
+    const int kin = (d.gnn.mlp_in.dims[0] + 31) >> 5;
+    if (decoder_zdim(d) == STRIVE_ZDIM && kin == 6) fn(integral_constant<int, 6>(), integral_constant<int, STRIVE_ZDIM>());
+    else if (kin == 5) fn(integral_constant<int, 5>(), integral_constant<int, 0>());
+    else if (kin == 6) fn(integral_constant<int, 6>(), integral_constant<int, 0>());
+    else fn(integral_constant<int, 7>(), integral_constant<int, 0>());
+}
 
 // =============================================================================================
 // host orchestration: forward
@@ -437,17 +454,23 @@ bool scene_tiles_on(const StriveDecoder* dec, const StriveScenes* sc) {
     return strive_tuning().scene_kernels != 0 && strive_tuning().scene_tiles != 0 && sc->max_n > scn::NR && scn::supported(*dec, *sc, true);
 }
 
-// more than 64 KB of LDS per workgroup needs the attribute, once per device
+// more than 64 KB of LDS per workgroup needs the attribute, once per device (every form of scene_form)
+template <int KIN, int ZFIX>
+bool scene_form_prepare() {
+    const int sweep = (int)scn::BwdLds<scn::sweep_zw(ZFIX)>::BYTES;
+    return hipFuncSetAttribute((const void*)scn::scene_fwd_step_kernel<false, KIN, ZFIX>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)scn::FwdLds::BYTES) != hipSuccess ||
+           hipFuncSetAttribute((const void*)scn::scene_fwd_step_kernel<true, KIN, ZFIX>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)scn::FwdLds::BYTES) != hipSuccess ||
+           hipFuncSetAttribute((const void*)scn::scene_bwd_sweep_kernel<false, false, ZFIX>, hipFuncAttributeMaxDynamicSharedMemorySize, sweep) != hipSuccess ||
+           hipFuncSetAttribute((const void*)scn::scene_bwd_sweep_kernel<true, false, ZFIX>, hipFuncAttributeMaxDynamicSharedMemorySize, sweep) != hipSuccess ||
+           hipFuncSetAttribute((const void*)scn::scene_bwd_sweep_kernel<false, true, ZFIX>, hipFuncAttributeMaxDynamicSharedMemorySize, sweep) != hipSuccess;
+}
+
 int scene_kernels_prepare() {
     static std::atomic<unsigned long long> done{0};
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev > 63) dev = 0;
     if (done.load(std::memory_order_acquire) & (1ull << dev)) return 0;
-    if (hipFuncSetAttribute((const void*)scn::scene_fwd_step_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)scn::FwdLds::BYTES) != hipSuccess ||
-        hipFuncSetAttribute((const void*)scn::scene_fwd_step_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)scn::FwdLds::BYTES) != hipSuccess ||
-        hipFuncSetAttribute((const void*)scn::scene_bwd_sweep_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)scn::BwdLds::BYTES) != hipSuccess ||
-        hipFuncSetAttribute((const void*)scn::scene_bwd_sweep_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)scn::BwdLds::BYTES) != hipSuccess ||
-        hipFuncSetAttribute((const void*)(scn::scene_bwd_sweep_kernel<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)scn::BwdLds::BYTES) != hipSuccess) {
+    if (scene_form_prepare<6, STRIVE_ZDIM>() || scene_form_prepare<5, 0>() || scene_form_prepare<6, 0>() || scene_form_prepare<7, 0>()) {
         strive_set_error("rollout: the scene kernels' LDS request was refused");
         return -1;
     }
@@ -499,13 +522,13 @@ GRUDev gru_dev(const StriveGRU& g) {
     return d;
 }
 
-FeatSrc decoder_features(const Tape& tp, int t, const float* sem, const float* z, const float* lw, int NC) {
+FeatSrc decoder_features(const Tape& tp, int t, const float* sem, const float* z, const float* lw, int NC, int Z) {
     FeatSrc f;
     f.n = 5;
     f.p[0] = tp.pf_t(t); f.w[0] = 64; f.per_agent[0] = 0;
     f.p[1] = tp.mf_t(t); f.w[1] = 64; f.per_agent[1] = 0;
     f.p[2] = sem;        f.w[2] = NC; f.per_agent[2] = 1;
-    f.p[3] = z;          f.w[3] = STRIVE_ZDIM; f.per_agent[3] = 0;
+    f.p[3] = z;          f.w[3] = Z;  f.per_agent[3] = 0;
     f.p[4] = lw;         f.w[4] = 2;  f.per_agent[4] = 1;
     return f;
 }
@@ -518,7 +541,10 @@ int check_decoder(const StriveDecoder* dec, const StriveScenes* sc, int FT) {
         strive_set_error("rollout: decoder_net must have D=64 and 2 (bicycle) or 4 (direct pose) outputs");
         return -1;
     }
-    if (dec->gnn.mlp_in.dims[0] != 64 + 64 + dec->gnn.NC + STRIVE_ZDIM + 2) { strive_set_error("rollout: decoder_net input width mismatch"); return -1; }
+    if (decoder_zdim(*dec) < 1 || decoder_zdim(*dec) > 64) {
+        strive_set_error("rollout: decoder_net input width mismatch (latent width Z = mlp_in.dims[0] - 130 - NC must be 1 .. 64)");
+        return -1;
+    }
     if (FT < 1 || sc->NA < 0 || sc->NS < 1) { strive_set_error("rollout: bad sizes"); return -1; }
     return 0;
 }
@@ -617,12 +643,15 @@ static int rollout_forward(const StriveDecoder* dec, const StriveScenes* sc, con
             a.par = dec->scene_par; a.traj = traj; a.KW = 0; a.part_a = part_a; a.part_arg = part_arg;
             auto launch_scene = [&](int mode, int ky = 1) {
                 a.mode = mode;
-                if (scene_prof)       // (tools/scene_phase_probe.py: phase ticks of workgroup 0 at the start of the workspace)
-                    hipLaunchKernelGGL(scn::scene_fwd_step_kernel<true>, dim3((unsigned)sc->B, (unsigned)ky), dim3(scn::NTHR), scn::FwdLds::BYTES, stream, gd,
-                                       gr, gf, dp, a, tp, (unsigned long long*)ws);
-                else
-                    hipLaunchKernelGGL(scn::scene_fwd_step_kernel<false>, dim3((unsigned)sc->B, (unsigned)ky), dim3(scn::NTHR), scn::FwdLds::BYTES, stream, gd,
-                                       gr, gf, dp, a, tp, (unsigned long long*)nullptr);
+                scene_form(*dec, [&](auto kin, auto zfix) {
+                    constexpr int KIN = decltype(kin)::value, ZFIX = decltype(zfix)::value;
+                    if (scene_prof)       // (tools/scene_phase_probe.py: phase ticks of workgroup 0 at the start of the workspace)
+                        hipLaunchKernelGGL((scn::scene_fwd_step_kernel<true, KIN, ZFIX>), dim3((unsigned)sc->B, (unsigned)ky), dim3(scn::NTHR),
+                                           scn::FwdLds::BYTES, stream, gd, gr, gf, dp, a, tp, (unsigned long long*)ws);
+                    else
+                        hipLaunchKernelGGL((scn::scene_fwd_step_kernel<false, KIN, ZFIX>), dim3((unsigned)sc->B, (unsigned)ky), dim3(scn::NTHR),
+                                           scn::FwdLds::BYTES, stream, gd, gr, gf, dp, a, tp, (unsigned long long*)nullptr);
+                });
             };
             if (scene_split && fwd_k > 0) {
                 // large scenes, round 5: K workgroups of the scene kernel per scene share the edge chunks (node phases repeated, partial
@@ -664,20 +693,23 @@ static int rollout_forward(const StriveDecoder* dec, const StriveScenes* sc, con
             a.t = t; a.FT = FT; a.NC = NC; a.max_n = sc->max_n; a.sem = sem; a.lw = lw; a.z = z; a.ext = ext_future; a.ptr = sc->ptr;
             a.par = dec->scene_par; a.traj = traj; a.KW = 0; a.part_a = nullptr; a.part_arg = nullptr;
             const dim3 grid((unsigned)sc->B, 1, (unsigned)((sc->max_n + scn::NR - 1) / scn::NR));
-            a.mode = 1;
-            hipLaunchKernelGGL(scn::scene_fwd_step_kernel<false>, grid, dim3(scn::NTHR), scn::FwdLds::BYTES, stream, gd, gr, gf, dp, a, tp,
-                               (unsigned long long*)nullptr);
-            hipLaunchKernelGGL(gnn_edge_kernel, dim3((unsigned)R), dim3(256), EdgeLds::bytes(), stream, gd, sd, tp.pos_t(t), gb);
-            a.mode = 4;
-            hipLaunchKernelGGL(scn::scene_fwd_step_kernel<false>, grid, dim3(scn::NTHR), scn::FwdLds::BYTES, stream, gd, gr, gf, dp, a, tp,
-                               (unsigned long long*)nullptr);
+            scene_form(*dec, [&](auto kin, auto zfix) {
+                constexpr int KIN = decltype(kin)::value, ZFIX = decltype(zfix)::value;
+                a.mode = 1;
+                hipLaunchKernelGGL((scn::scene_fwd_step_kernel<false, KIN, ZFIX>), grid, dim3(scn::NTHR), scn::FwdLds::BYTES, stream, gd, gr, gf, dp,
+                                   a, tp, (unsigned long long*)nullptr);
+                hipLaunchKernelGGL(gnn_edge_kernel, dim3((unsigned)R), dim3(256), EdgeLds::bytes(), stream, gd, sd, tp.pos_t(t), gb);
+                a.mode = 4;
+                hipLaunchKernelGGL((scn::scene_fwd_step_kernel<false, KIN, ZFIX>), grid, dim3(scn::NTHR), scn::FwdLds::BYTES, stream, gd, gr, gf, dp,
+                                   a, tp, (unsigned long long*)nullptr);
+            });
             if (t < FT - 1) {
                 int rc = encode_step(t);
                 if (rc) return rc;
             }
             continue;
         }
-        FeatSrc f = decoder_features(tp, t, sem, z, lw, NC);
+        FeatSrc f = decoder_features(tp, t, sem, z, lw, NC, decoder_zdim(*dec));
         hipLaunchKernelGGL(gnn_node1_kernel, dim3(nb), dim3(256), Node1Lds::bytes(in_ld1, xs_ld), stream, gd, sc->NS, f, sem,
                            gb, (int)R);
         hipLaunchKernelGGL(gnn_edge_kernel, dim3((unsigned)R), dim3(256), EdgeLds::bytes(), stream, gd, sd, tp.pos_t(t), gb);
@@ -1177,7 +1209,7 @@ int rollout_backward(const StriveDecoder* dec, const StriveScenes* sc, const flo
     hipMemsetAsync(d_loc, 0, R * 4 * 4, stream);
     hipMemsetAsync(g_pf, 0, R * 64 * 4, stream);
     hipMemsetAsync(g_mem, 0, R * 192 * 4, stream);
-    hipMemsetAsync(dz, 0, R * STRIVE_ZDIM * 4, stream);
+    hipMemsetAsync(dz, 0, R * decoder_zdim(*dec) * 4, stream);
 
     for (int t = FT - 1; t >= 0; --t) {
         GnnBuffers g2;
@@ -1188,7 +1220,7 @@ int rollout_backward(const StriveDecoder* dec, const StriveScenes* sc, const flo
         g2.Q = tp.Q_t(t);
         g2.PRE_IN = tp.PRE_IN_t(t);
         g2.PRE_E = tp.PRE_E_t(t);
-        FeatSrc f = decoder_features(tp, t, sem, z, lw, NC);
+        FeatSrc f = decoder_features(tp, t, sem, z, lw, NC, decoder_zdim(*dec));
         if (t < FT - 1)
             hipLaunchKernelGGL(gru_bwd_kernel<WG>, dim3(nb), dim3(256), gru_bwd_lds_bytes(), stream, gr, ggr, tp, t, (int)R, g_pf,
                                g_mem, d_loc);
@@ -1285,30 +1317,34 @@ extern "C" int strive_rollout_bwd(const StriveDecoder* dec, const StriveScenes* 
         int K = chunks >= 3 ? chunks : 0;
         if (strive_tuning().sweep_step >= 0) K = strive_tuning().sweep_step;
         if (K > 4) K = 4;
-        const size_t need = (size_t)sc->B * (K > 0 ? K : 1) * (2 * scn::SWEEP_PART_FLOATS + scn::SWEEP_STATE_FLOATS) * 4 + 512;
-        if (K >= 1 && !prof && ws_bytes >= need) {
-            a.K = K;
-            a.part = reinterpret_cast<float*>((char*)ws + 256);
-            a.state = a.part + 2 * (size_t)sc->B * K * scn::SWEEP_PART_FLOATS;
-            const GNNDev gd = gnn_dev(dec->gnn);
-            const GRUDev gr = gru_dev(dec->gru);
-            const scn::GRUFrag gf = scn::gru_frag(dec->gru);
-            const DynParams dp = dyn_params(*dec);
-            for (int t = FT - 1; t >= -1; --t) {
-                a.t = t;
-                hipLaunchKernelGGL((scn::scene_bwd_sweep_kernel<false, true>), dim3((unsigned)sc->B, (unsigned)K), dim3(scn::NTHR), scn::BwdLds::BYTES,
-                                   (hipStream_t)stream_, gd, gr, gf, dp, a, tp, (unsigned long long*)nullptr);
+        scene_form(*dec, [&](auto, auto zfix) {
+            constexpr int ZFIX = decltype(zfix)::value;
+            constexpr size_t LDS = scn::BwdLds<scn::sweep_zw(ZFIX)>::BYTES;
+            const size_t need =
+                (size_t)sc->B * (K > 0 ? K : 1) * (2 * scn::SWEEP_PART_FLOATS + scn::sweep_state_floats(scn::sweep_zw(ZFIX))) * 4 + 512;
+            if (K >= 1 && !prof && ws_bytes >= need) {
+                a.K = K;
+                a.part = reinterpret_cast<float*>((char*)ws + 256);
+                a.state = a.part + 2 * (size_t)sc->B * K * scn::SWEEP_PART_FLOATS;
+                const GNNDev gd = gnn_dev(dec->gnn);
+                const GRUDev gr = gru_dev(dec->gru);
+                const scn::GRUFrag gf = scn::gru_frag(dec->gru);
+                const DynParams dp = dyn_params(*dec);
+                for (int t = FT - 1; t >= -1; --t) {
+                    a.t = t;
+                    hipLaunchKernelGGL((scn::scene_bwd_sweep_kernel<false, true, ZFIX>), dim3((unsigned)sc->B, (unsigned)K), dim3(scn::NTHR), LDS,
+                                       (hipStream_t)stream_, gd, gr, gf, dp, a, tp, (unsigned long long*)nullptr);
+                }
+                return;
             }
-            STRIVE_CHECK_LAUNCH();
-            return 0;
-        }
-        a.t = 0; a.K = 1; a.part = nullptr; a.state = nullptr;
-        if (prof)
-            hipLaunchKernelGGL(scn::scene_bwd_sweep_kernel<true>, dim3((unsigned)sc->B), dim3(scn::NTHR), scn::BwdLds::BYTES, (hipStream_t)stream_,
-                               gnn_dev(dec->gnn), gru_dev(dec->gru), scn::gru_frag(dec->gru), dyn_params(*dec), a, tp, (unsigned long long*)ws + 32);
-        else
-            hipLaunchKernelGGL(scn::scene_bwd_sweep_kernel<false>, dim3((unsigned)sc->B), dim3(scn::NTHR), scn::BwdLds::BYTES, (hipStream_t)stream_,
-                               gnn_dev(dec->gnn), gru_dev(dec->gru), scn::gru_frag(dec->gru), dyn_params(*dec), a, tp, (unsigned long long*)nullptr);
+            a.t = 0; a.K = 1; a.part = nullptr; a.state = nullptr;
+            if (prof)
+                hipLaunchKernelGGL((scn::scene_bwd_sweep_kernel<true, false, ZFIX>), dim3((unsigned)sc->B), dim3(scn::NTHR), LDS, (hipStream_t)stream_,
+                                   gnn_dev(dec->gnn), gru_dev(dec->gru), scn::gru_frag(dec->gru), dyn_params(*dec), a, tp, (unsigned long long*)ws + 32);
+            else
+                hipLaunchKernelGGL((scn::scene_bwd_sweep_kernel<false, false, ZFIX>), dim3((unsigned)sc->B), dim3(scn::NTHR), LDS, (hipStream_t)stream_,
+                                   gnn_dev(dec->gnn), gru_dev(dec->gru), scn::gru_frag(dec->gru), dyn_params(*dec), a, tp, (unsigned long long*)nullptr);
+        });
         STRIVE_CHECK_LAUNCH();
         return 0;
     }

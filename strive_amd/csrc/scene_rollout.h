@@ -24,6 +24,18 @@ constexpr int NR = 16;             // node rows of a scene (one matrix tile)
 constexpr int EC = 64;             // edge rows per chunk (four tiles)
 constexpr int XLD = 68;            // leading dimension of 64-wide LDS rows
 constexpr int GLDS = 196;          // ... of 192-wide rows (GRU gate pre-activations, mlp_in features)
+constexpr int ZMAX = 64;           // widest latent the kernels take (include/strive_hip.h STRIVE_ZDIM)
+
+// Latent widths.  decoder_net's input is [past_feat 64 | map_feat 64 | sem NC | z Z | lw 2]; Z comes from the decoder pack
+// (rollout.hip decoder_zdim).  The kernels take two template parameters for it:
+//   KIN  = k-steps of mlp_in's first layer, ceil((130 + NC + Z) / 32): 5, 6 or 7 for NC <= 8 and Z <= 64;
+//   ZFIX = the latent width compiled in (STRIVE_ZDIM: the shipped model, whose instructions stay those of a fixed width), or 0 =
+//          read from the weight descriptor (g.mlp_in.dims[0]) at run time.
+// The mlp_in features' LDS rows hold KIN * 32 values: stride GLDS up to 192, GLDS + 32 (same bank offset) for 224.
+template <int ZFIX>
+__device__ __forceinline__ int latent_width(const GNNDev& g, int NC) { return ZFIX ? ZFIX : g.mlp_in.dims[0] - (64 + 64 + NC + 2); }
+template <int KIN>
+constexpr int in_lds() { return KIN <= 6 ? GLDS : GLDS + 32; }
 
 // Compiler-only fence.  The sweep kernel is one long loop over steps and edge chunks; without it the loop-invariant parameter
 // loads of EVERY phase (LayerNorm affine terms, W_rel, the last layer's rows: ~200 registers) are hoisted to the kernel's
@@ -70,9 +82,11 @@ static inline bool supported(const StriveDecoder& d, const StriveScenes& sc, boo
     if (sc.NS != 1 || (sc.max_n > NR && !any_size) || sc.max_n < 1 || !d.scene_par) return false;
     if (d.gnn.D != 64 || d.gnn.NC > 8) return false;
     if (d.gnn.mlp_out.dims[3] != 2) return false;        // the bicycle head only (Par packs a 2-wide mlp_out; direct output: rollout.hip)
-    // k-step counts the kernels are written for: mlp_in 162 + NC -> 6, edge layer 0 (132 + 2 NC: sem_i, sem_j and the relative
-    // pose share the 5th step), update 128 + NC -> 5
-    if (((d.gnn.mlp_in.dims[0] + 31) >> 5) != 6 || ((d.gnn.edge.dims[0] + 31) >> 5) != 5 || ((d.gnn.update.dims[0] + 31) >> 5) != 5) return false;
+    // k-step counts the kernels are written for: mlp_in 130 + NC + Z -> 5, 6 or 7 (template parameter KIN; Z <= 64), edge layer 0
+    // (132 + 2 NC: sem_i, sem_j and the relative pose share the 5th step), update 128 + NC -> 5
+    const int Z = d.gnn.mlp_in.dims[0] - (64 + 64 + d.gnn.NC + 2), kin = (d.gnn.mlp_in.dims[0] + 31) >> 5;
+    if (Z < 1 || Z > ZMAX || kin < 5 || kin > 7) return false;
+    if (((d.gnn.edge.dims[0] + 31) >> 5) != 5 || ((d.gnn.update.dims[0] + 31) >> 5) != 5) return false;
     const StriveMLP* ms[4] = {&d.gnn.mlp_in, &d.gnn.edge, &d.gnn.update, &d.gnn.mlp_out};
     for (int i = 0; i < 4; ++i)
         for (int l = 0; l < ms[i]->nlayers; ++l) {
@@ -499,6 +513,10 @@ struct FwdLds {
     }
 };
 
+// the widest mlp_in feature rows (KIN = 7) fit the scratch region and the split buffer sized for 192-wide ones
+static_assert(NR * in_lds<7>() + 3 * NR * HLD <= FwdLds::U_FLOATS && SB::bytes(7 * 32, NR) <= FwdLds::SB_BYTES,
+              "mlp_in rows of 224 values do not fit the forward step's LDS");
+
 struct StepArgsS {
     int t, FT, NC, max_n;
     int mode;                  // bit 0: features .. edge partials (x, P, Q into the tape); bit 1: the edge chunks (running max);
@@ -507,7 +525,7 @@ struct StepArgsS {
                                // rows are 3-4 chunks on ONE CU here and one workgroup per target there
     const float* sem;          // (NA, NC)
     const float* lw;           // (NA, 2) normalised
-    const float* z;            // (NA, 32)
+    const float* z;            // (NA, Z)
     const float* ext;          // (B, FT, 4) or null
     const int32_t* ptr;        // (B + 1)
     const float* par;          // StriveDecoder.scene_par
@@ -522,9 +540,9 @@ struct StepArgsS {
 };
 
 // =====================================================================================================================
-// forward: one decoder step of one scene.   grid = B (x K, see StepArgsS::KW), block = 512
+// forward: one decoder step of one scene.   grid = B (x K, see StepArgsS::KW), block = 512;  KIN, ZFIX: see latent_width
 // =====================================================================================================================
-template <bool PROF>
+template <bool PROF, int KIN, int ZFIX>
 static __global__ __launch_bounds__(NTHR) void scene_fwd_step_kernel(GNNDev g, GRUDev gru, GRUFrag gf, DynParams dp, StepArgsS a,
                                                                      Tape tp, unsigned long long* prof) {
     HIP_DYNAMIC_SHARED(float, smem)
@@ -550,13 +568,15 @@ static __global__ __launch_bounds__(NTHR) void scene_fwd_step_kernel(GNNDev g, G
             tick = now_;                                                    \
         }                                                                   \
     } while (0)
-    const int F = 64 + 64 + NC + STRIVE_ZDIM + 2;                 // decoder_net input (traffic_model.py:628-629)
-    float* s_in = L.U;                                            // [NR][GLDS]
-    float* s_pre = L.U + NR * GLDS;                               // [3][NR][HLD]
+    const int Z = latent_width<ZFIX>(g, NC);
+    const int F = 64 + 64 + NC + Z + 2;                           // decoder_net input (traffic_model.py:628-629)
+    constexpr int ILD = in_lds<KIN>();
+    float* s_in = L.U;                                            // [NR][ILD]
+    float* s_pre = L.U + NR * ILD;                                // [3][NR][HLD]
     // requested first: the weight tiles of the first product and of the edge loop (kept across all chunks), and the GRU's
     // hidden inputs of this step
-    AF<6> f_in0;
-    af_first<6>(f_in0, g.mlp_in.wf[0], 0, 8, 1, tid);
+    AF<KIN> f_in0;
+    af_first<KIN>(f_in0, g.mlp_in.wf[0], 0, 8, 1, tid);
     AF<4> f_e1, f_e2;
     af_first<4>(f_e1, g.edge.wf[1], 0, 8, 4, tid);
     af_first<4>(f_e2, g.edge.wf[2], 0, 4, 4, tid);
@@ -579,9 +599,9 @@ static __global__ __launch_bounds__(NTHR) void scene_fwd_step_kernel(GNNDev g, G
         if (k < 64) v = tp.pf_t(t)[(size_t)r * 64 + k];
         else if (k < 128) v = tp.mf_t(t)[(size_t)r * 64 + (k - 64)];
         else if (k < 128 + NC) v = a.sem[(size_t)r * NC + (k - 128)];
-        else if (k < 128 + NC + STRIVE_ZDIM) v = a.z[(size_t)r * STRIVE_ZDIM + (k - 128 - NC)];
-        else v = a.lw[(size_t)r * 2 + (k - 128 - NC - STRIVE_ZDIM)];
-        s_in[rr * GLDS + k] = v;
+        else if (k < 128 + NC + Z) v = a.z[(size_t)r * Z + (k - 128 - NC)];
+        else v = a.lw[(size_t)r * 2 + (k - 128 - NC - Z)];
+        s_in[rr * ILD + k] = v;
     }
     if (tid < n * 4) L.pos[tid] = tp.pos_t(t)[(size_t)lo * 4 + tid];
     for (int i = tid; i < NR * 64; i += NTHR) { L.A[i] = 0.f; L.ARG[i] = -1; }
@@ -590,10 +610,10 @@ static __global__ __launch_bounds__(NTHR) void scene_fwd_step_kernel(GNNDev g, G
 
     // ---- mlp_in: F -> 128 -> 128 -> 64 ----
     {
-        SB sb(L.sb, L.rs, 192, NR);
-        split16([&](int r, int k) { return s_in[r * GLDS + k]; }, F, 192, n, NR, sb, tid);
+        SB sb(L.sb, L.rs, KIN * 32, NR);
+        split16([&](int r, int k) { return s_in[r * ILD + k]; }, F, KIN * 32, n, NR, sb, tid);
         __syncthreads();
-        dense_rows<6>(g.mlp_in.wf[0], g.mlp_in.wsc[0], (L.par + Par::IN_B0), H, 1, n, sb, s_pre, HLD, tid, &f_in0);
+        dense_rows<KIN>(g.mlp_in.wf[0], g.mlp_in.wsc[0], (L.par + Par::IN_B0), H, 1, n, sb, s_pre, HLD, tid, &f_in0);
         __syncthreads();
     }
     {
@@ -975,8 +995,10 @@ static __global__ __launch_bounds__(NTHR) void scene_fwd_step_kernel(GNNDev g, G
 
 // =====================================================================================================================
 // backward: the whole reverse-time sweep of one scene in one launch.   grid = B, block = 512
-//   d_traj (NA, FT, 4) -> dz (NA, 32); reads the tape of the forward sweep (pre-activations, gates, arg-max, poses).
+//   d_traj (NA, FT, 4) -> dz (NA, Z); reads the tape of the forward sweep (pre-activations, gates, arg-max, poses).
+//   ZW = columns of the dz rows in LDS: ZFIX, or ZMAX for a width read at run time (the rows hold Z values, packed).
 // =====================================================================================================================
+template <int ZW>
 struct BwdLds {
     // adjoint state carried from step t + 1 to step t
     float* g_state;  // [NR][8]
@@ -984,7 +1006,7 @@ struct BwdLds {
     float* d_loc;    // [NR][4]    adjoint of the local pose fed to the GRU
     float* g_pf;     // [NR][XLD]  adjoint of past_feat_{t+1}
     float* g_mem;    // [3][NR][XLD]
-    float* dz;       // [NR][32]
+    float* dz;       // [NR][ZW]   (row stride Z)
     // per step
     float* pos;      // [NR][4]
     float* dP;       // [NR][HLD]
@@ -1003,7 +1025,7 @@ struct BwdLds {
     float* par;      // [Par::FLOATS]
     static constexpr int SB_BYTES = SB::bytes(128, EC) > 2 * SB::bytes(192, NR) ? SB::bytes(128, EC) : 2 * SB::bytes(192, NR);
     static constexpr int U_FLOATS = EC * HLD + 3 * EC * 4 > 2 * NR * GLDS + NR * XLD ? EC * HLD + 3 * EC * 4 : 2 * NR * GLDS + NR * XLD;
-    static constexpr int P_FLOATS = NR * 8 + NR * 4 + NR * 4 + NR * XLD + 3 * NR * XLD + NR * 32 + NR * 4 + 2 * NR * HLD + NR * 4 + NR * HLD +
+    static constexpr int P_FLOATS = NR * 8 + NR * 4 + NR * 4 + NR * XLD + 3 * NR * XLD + NR * ZW + NR * 4 + 2 * NR * HLD + NR * 4 + NR * HLD +
                                     NR * 64 + NR * 4 + EC + EC * 4 + 3 * EC;
     static constexpr size_t BYTES = (size_t)P_FLOATS * 4 + SB_BYTES + (size_t)(U_FLOATS + Par::FLOATS) * 4 + 64;
     __device__ BwdLds(float* base) {
@@ -1013,7 +1035,7 @@ struct BwdLds {
         g_pf = d_loc + NR * 4;
         g_mem = g_pf + NR * XLD;
         dz = g_mem + 3 * NR * XLD;
-        pos = dz + NR * 32;
+        pos = dz + NR * ZW;
         dP = pos + NR * 4;
         dQ = dP + NR * HLD;
         gpos_n = dQ + NR * HLD;
@@ -1030,7 +1052,9 @@ struct BwdLds {
         par = U + U_FLOATS;
     }
 };
-static_assert(BwdLds::P_FLOATS % 4 == 0, "split buffer must stay 16-byte aligned");
+static_assert(BwdLds<STRIVE_ZDIM>::P_FLOATS % 4 == 0 && BwdLds<ZMAX>::P_FLOATS % 4 == 0, "split buffer must stay 16-byte aligned");
+// dz columns in LDS for a sweep form
+constexpr int sweep_zw(int zfix) { return zfix ? zfix : ZMAX; }
 
 struct SweepArgs {
     int FT, NC, max_n;
@@ -1040,16 +1064,16 @@ struct SweepArgs {
     const int32_t* ptr;
     const float* par;          // StriveDecoder.scene_par
     const float* g_traj;       // (NA, FT, 4)
-    float* dz;                 // (NA, 32)
+    float* dz;                 // (NA, Z)
     // stepwise form only (scene_bwd_sweep_kernel<PROF, true>): the step of this launch, workgroups per scene, and the two global
     // buffers that carry a scene's sweep from launch to launch
     int t, K;
     float* part;               // (2, B, K, PART_FLOATS)   dP | dQ | gpos_n of the edge chunks workgroup k walked, by step parity:
                                // the launch of step t reads the sums of step t + 1 while its workgroups write those of step t
-    float* state;              // (B, K, STATE_FLOATS)  g_state | g_mem | dz | gin2 of workgroup k (all K hold the same values)
+    float* state;              // (B, K, sweep_state_floats(ZW))  g_state | g_mem | dz | gin2 of workgroup k (all K hold the same values)
 };
 constexpr int SWEEP_PART_FLOATS = 2 * NR * HLD + NR * 4;
-constexpr int SWEEP_STATE_FLOATS = NR * 8 + 3 * NR * XLD + NR * 32 + NR * HLD;
+constexpr int sweep_state_floats(int zw) { return NR * 8 + 3 * NR * XLD + NR * zw + NR * HLD; }
 
 // one product of the sweep with a caller-supplied epilogue (identity k-step lists)
 template <int NK, typename Epi>
@@ -1072,13 +1096,17 @@ __device__ __forceinline__ void dense_rows_epi(const uint4* __restrict__ frag, f
 // t = [finish step t + 1] -> GRU(t) -> dynamics .. update(t) -> own edge chunks of t; the launch with t = -1 finishes step 0 and
 // writes dz.  With one chunk per workgroup (n (n - 1) <= 64 K) every sum is formed in the order of the one-launch sweep: the two
 // forms give the same bits (tests/test_emu_kernels.py).
-template <bool PROF, bool STEP = false>
+// ZFIX: see latent_width.  (The sweep's products over mlp_in run over its 128 hidden channels, so mlp_in's k-step count KIN
+// does not enter here; the latent width sets the dz columns of layer 0's adjoint that are kept.)
+template <bool PROF, bool STEP, int ZFIX>
 static __global__ __launch_bounds__(NTHR) void scene_bwd_sweep_kernel(GNNDev g, GRUDev gru, GRUFrag gf, DynParams dp, SweepArgs a,
                                                                       Tape tp, unsigned long long* prof) {
     HIP_DYNAMIC_SHARED(float, smem)
-    BwdLds L(smem);
+    constexpr int ZW = sweep_zw(ZFIX), STATE_FLOATS = sweep_state_floats(ZW);
+    BwdLds<ZW> L(smem);
     int tid = threadIdx.x;
     const int b = blockIdx.x, NC = a.NC, H = STRIVE_HID, FT = a.FT;
+    const int Z = latent_width<ZFIX>(g, NC);
     const int kw = STEP ? (int)blockIdx.y : 0, KW = STEP ? a.K : 1;
     const int lo = a.ptr[b], n = a.ptr[b + 1] - lo;
     if (n <= 0) return;
@@ -1098,7 +1126,7 @@ static __global__ __launch_bounds__(NTHR) void scene_bwd_sweep_kernel(GNNDev g, 
     for (int i = tid; i < NR * 4; i += NTHR) { L.g_pos[i] = 0.f; L.d_loc[i] = 0.f; L.gpos_n[i] = 0.f; }
     for (int i = tid; i < NR * XLD; i += NTHR) L.g_pf[i] = 0.f;
     for (int i = tid; i < 3 * NR * XLD; i += NTHR) L.g_mem[i] = 0.f;
-    for (int i = tid; i < NR * 32; i += NTHR) L.dz[i] = 0.f;
+    for (int i = tid; i < NR * ZW; i += NTHR) L.dz[i] = 0.f;
     for (int i = tid; i < NR * HLD; i += NTHR) { L.dP[i] = 0.f; L.dQ[i] = 0.f; }
     par_stage(L.par, a.par, tid);
     SCN_SYNC(tid);
@@ -1534,8 +1562,11 @@ static __global__ __launch_bounds__(NTHR) void scene_bwd_sweep_kernel(GNNDev g, 
 #pragma unroll
                 for (int r = 0; r < 4; ++r) s_ga[row * HLD + c0 + r] = v[r];
             }, &f_i1);
+            // the latent columns [128 + NC, 128 + NC + Z) lie in channel tiles 8 .. ztl + 7 (NC <= 8)
+            const int Zs = ZFIX ? ZFIX : Z;                     // (a compile-time constant in the fixed-width form)
+            const int ztl = ZFIX ? 3 : ((128 + NC + Zs + 15) >> 4) - 8;
             af_first<4>(f_i0a, g.mlp_in.wbf[0], 0, 4, 1, tid);
-            af_first<4>(f_i0b, g.mlp_in.wbf[0], 8, 3, 1, tid);
+            af_first<4>(f_i0b, g.mlp_in.wbf[0], 8, ztl, 1, tid);
             SCN_SYNC(tid);
             ln_relu_bwd16<1>(x_i0,
                              [&](int r, int k0, float (&d)[8]) {
@@ -1544,17 +1575,17 @@ static __global__ __launch_bounds__(NTHR) void scene_bwd_sweep_kernel(GNNDev g, 
                              },
                              n, NR, (L.par + Par::IN_G0), (L.par + Par::IN_E0), &sb, nullptr, 0, tid);
             SCN_SYNC(tid);
-            // layer 0 (F <- 128): only the past_feat columns [0, 64) and the latent columns [128 + NC, 160 + NC) are wanted
+            // layer 0 (F <- 128): only the past_feat columns [0, 64) and the latent columns [128 + NC, 128 + NC + Z) are wanted
             dense_rows_epi<4>(g.mlp_in.wbf[0], g.mlp_in.wsc[0], 0, 4, 1, sb, tid, [&](int row, int c0, const float (&v)[4]) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) L.g_pf[row * XLD + c0 + r] = v[r];
             }, &f_i0a);
             const int zoff = 128 + NC;
-            dense_rows_epi<4>(g.mlp_in.wbf[0], g.mlp_in.wsc[0], 8, 3, 1, sb, tid, [&](int row, int c0, const float (&v)[4]) {
+            dense_rows_epi<4>(g.mlp_in.wbf[0], g.mlp_in.wsc[0], 8, ztl, 1, sb, tid, [&](int row, int c0, const float (&v)[4]) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int c = c0 + r - zoff;
-                    if (c >= 0 && c < STRIVE_ZDIM) L.dz[row * 32 + c] += v[r];
+                    if (c >= 0 && c < Zs) L.dz[row * Zs + c] += v[r];
                 }
             }, &f_i0b);
             SCN_SYNC(tid);
@@ -1569,16 +1600,16 @@ static __global__ __launch_bounds__(NTHR) void scene_bwd_sweep_kernel(GNNDev g, 
             sec_edges(t, 0, EC);
             sec_node1(t);
         }
-        for (int i = tid; i < n * STRIVE_ZDIM; i += NTHR) a.dz[(size_t)lo * STRIVE_ZDIM + i] = L.dz[i];
+        for (int i = tid; i < n * Z; i += NTHR) a.dz[(size_t)lo * Z + i] = L.dz[i];
     } else {
         const int t = a.t;
-        float* st = a.state + ((size_t)b * KW + kw) * SWEEP_STATE_FLOATS;
+        float* st = a.state + ((size_t)b * KW + kw) * STATE_FLOATS;
         if (t < FT - 1) {
             // this workgroup's state of the previous launch ...
             for (int i = tid; i < NR * 8; i += NTHR) L.g_state[i] = st[i];
             for (int i = tid; i < 3 * NR * XLD; i += NTHR) L.g_mem[i] = st[NR * 8 + i];
-            for (int i = tid; i < NR * 32; i += NTHR) L.dz[i] = st[NR * 8 + 3 * NR * XLD + i];
-            for (int i = tid; i < NR * HLD; i += NTHR) L.gin2[i] = st[NR * 8 + 3 * NR * XLD + NR * 32 + i];
+            for (int i = tid; i < NR * ZW; i += NTHR) L.dz[i] = st[NR * 8 + 3 * NR * XLD + i];
+            for (int i = tid; i < NR * HLD; i += NTHR) L.gin2[i] = st[NR * 8 + 3 * NR * XLD + NR * ZW + i];
             // ... and the chunk sums of step t + 1 of ALL workgroups of the scene that had chunks, added in workgroup order
             const int nchunk = (E + EC - 1) / EC, kb = nchunk < KW ? nchunk : KW;
             const float* part_prev = a.part + (size_t)((t + 1) & 1) * gridDim.x * KW * SWEEP_PART_FLOATS;
@@ -1609,10 +1640,10 @@ static __global__ __launch_bounds__(NTHR) void scene_bwd_sweep_kernel(GNNDev g, 
             if (tid < NR * 4) pk[2 * NR * HLD + tid] = L.gpos_n[tid];
             for (int i = tid; i < NR * 8; i += NTHR) st[i] = L.g_state[i];
             for (int i = tid; i < 3 * NR * XLD; i += NTHR) st[NR * 8 + i] = L.g_mem[i];
-            for (int i = tid; i < NR * 32; i += NTHR) st[NR * 8 + 3 * NR * XLD + i] = L.dz[i];
-            for (int i = tid; i < NR * HLD; i += NTHR) st[NR * 8 + 3 * NR * XLD + NR * 32 + i] = L.gin2[i];
+            for (int i = tid; i < NR * ZW; i += NTHR) st[NR * 8 + 3 * NR * XLD + i] = L.dz[i];
+            for (int i = tid; i < NR * HLD; i += NTHR) st[NR * 8 + 3 * NR * XLD + NR * ZW + i] = L.gin2[i];
         } else if (kw == 0) {
-            for (int i = tid; i < n * STRIVE_ZDIM; i += NTHR) a.dz[(size_t)lo * STRIVE_ZDIM + i] = L.dz[i];
+            for (int i = tid; i < n * Z; i += NTHR) a.dz[(size_t)lo * Z + i] = L.dz[i];
         }
     }
 #undef SCN_TICK

@@ -14,8 +14,10 @@ Both output parameterisations of the reference are served: ``output_bicycle=True
 and yaw rate, go through the kinematic bicycle model; ``set_bicycle_params`` must be called) and ``output_bicycle=False``
 (``--no_output_bicycle``: the decoder's 4 outputs are each step's local pose, no bicycle parameters).
 
-Not supported (raise NotImplementedError): ``traj_encoder='gru'`` and non-default map-CNN shapes -- no shipped config uses
-them (last paragraph).
+``latent_size`` (the drivers' ``--latent_size``) may be any width from 1 to 64; 32 is the shipped one.
+
+Not supported (raise NotImplementedError): ``traj_encoder='gru'``, feature sizes other than 64, latent sizes above 64 and
+non-default map-CNN shapes -- no shipped config uses them (last paragraph).
 """
 import os
 
@@ -47,8 +49,12 @@ class TrafficModel(nn.Module):
         if (list(conv_kernel_list), list(conv_stride_list), list(conv_filter_list), conv_channel_in, map_obs_size_pix) != \
                 ([7, 5, 5, 3, 3, 3], [2] * 6, [16, 32, 64, 64, 128, 128], 4, 256):
             raise NotImplementedError('strive_amd implements the default map CNN (4x256x256 crop, 6 stride-2 convs) only')
-        if (map_feat_size, past_feat_size, future_feat_size, latent_size) != (64, 64, 64, 32):
-            raise NotImplementedError('strive_amd kernels are built for feature size 64 and latent size 32')
+        if (map_feat_size, past_feat_size, future_feat_size) != (64, 64, 64):
+            raise NotImplementedError('strive_amd kernels are built for feature size 64 (map_feat_size, past_feat_size, '
+                                      'future_feat_size), got (%d, %d, %d)' % (map_feat_size, past_feat_size, future_feat_size))
+        if not 1 <= int(latent_size) <= 64:
+            # the prior / posterior nets output 2 * latent_size values: the MLP and GNN kernels allow up to 128
+            raise NotImplementedError('strive_amd kernels support latent_size from 1 to 64, got latent_size=%d' % latent_size)
         self.normalizer = self.att_normalizer = None
         self.PT, self.FT, self.NC = npast, nfuture, nclasses
         self.dt = 0.5

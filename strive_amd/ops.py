@@ -651,7 +651,7 @@ class _RolloutFn(torch.autograd.Function):
     def forward(ctx, z, h):
         lib = h.lib
         dev = z.device
-        zz = _f32c(z).reshape(h.R, 32)
+        zz = _f32c(z).reshape(h.R, h.Z)
         traj = torch.empty((h.R, h.FT, 4), dtype=torch.float32, device=dev)
         tape = torch.empty(h.tape_bytes, dtype=torch.uint8, device=dev)
         ws = _workspace(dev, h.ws_bytes, 'rollout')
@@ -668,7 +668,7 @@ class _RolloutFn(torch.autograd.Function):
     def backward(ctx, d_traj):
         h = ctx.h
         dev = d_traj.device
-        dz = torch.empty((h.R, 32), dtype=torch.float32, device=dev)
+        dz = torch.empty((h.R, h.Z), dtype=torch.float32, device=dev)
         ws = _workspace(dev, h.ws_bytes, 'rollout')
         h.lib.call('strive_rollout_bwd', h.dec.ref(), h.sc.ref(), L.ptr(h.lw), L.ptr(h.sem), L.ptr(ctx.zz), L.ptr(h.ext),
                    h.FT, L.ptr(_f32c(d_traj)), L.ptr(dz), L.ptr(ctx.tape), ctx.tape.numel(), L.ptr(ws), ws.numel(),
@@ -698,7 +698,7 @@ class _RolloutPairFn(torch.autograd.Function):
             if not torch.equal(z_a.detach(), z_b.detach()):
                 raise ValueError('decode_embedding_pair: the two latents must hold the same values (complementary detach of the '
                                  'same leaves); use two decode_embedding calls for different latents')
-        zz = _f32c(z_a).reshape(h.R, 32)
+        zz = _f32c(z_a).reshape(h.R, h.Z)
         traj = torch.empty((h.R, h.FT, 4), dtype=torch.float32, device=dev)
         tape = torch.empty(h.tape_bytes, dtype=torch.uint8, device=dev)
         ws = _workspace(dev, h.ws_bytes, 'rollout')
@@ -719,7 +719,7 @@ class _RolloutPairFn(torch.autograd.Function):
         ws = _workspace(dev, h.ws_bytes, 'rollout')
 
         def sweep(d_traj):
-            dz = torch.empty((h.R, 32), dtype=torch.float32, device=dev)
+            dz = torch.empty((h.R, h.Z), dtype=torch.float32, device=dev)
             h.lib.call('strive_rollout_bwd', h.dec.ref(), h.sc.ref(), L.ptr(h.lw), L.ptr(h.sem), L.ptr(ctx.zz), L.ptr(h.ext),
                        h.FT, L.ptr(d_traj), L.ptr(dz), L.ptr(ctx.tape), ctx.tape.numel(), L.ptr(ws), ws.numel(), _stream(d_traj))
             return dz
@@ -742,7 +742,7 @@ class _RolloutPairFn(torch.autograd.Function):
                 side.wait_stream(cur)
                 with torch.cuda.stream(side):
                     ws_b = _workspace(dev, h.ws_bytes, 'rollout')          # (scratch is per stream)
-                    dzb = torch.empty((h.R, 32), dtype=torch.float32, device=dev)
+                    dzb = torch.empty((h.R, h.Z), dtype=torch.float32, device=dev)
                     h.lib.call('strive_rollout_bwd', h.dec.ref(), h.sc.ref(), L.ptr(h.lw), L.ptr(h.sem), L.ptr(ctx.zz), L.ptr(h.ext),
                                h.FT, L.ptr(db), L.ptr(dzb), L.ptr(ctx.tape), ctx.tape.numel(), L.ptr(ws_b), ws_b.numel(), _stream(db))
                 db.record_stream(side)
@@ -765,7 +765,7 @@ class _RolloutTrainFn(torch.autograd.Function):
     def forward(ctx, z, past_feat, map_feat, h, *ps):
         lib = h.lib
         dev = z.device
-        zz = z.to(torch.float32).contiguous().reshape(h.R, 32)
+        zz = z.to(torch.float32).contiguous().reshape(h.R, h.Z)
         pf = past_feat.to(torch.float32).contiguous()
         mf = map_feat.to(torch.float32).contiguous()
         traj = torch.empty((h.R, h.FT, 4), dtype=torch.float32, device=dev)
@@ -790,7 +790,7 @@ class _RolloutTrainFn(torch.autograd.Function):
         h = ctx.h
         lib = h.lib
         dev = d_traj.device
-        dz = torch.empty((h.R, 32), dtype=torch.float32, device=dev)
+        dz = torch.empty((h.R, h.Z), dtype=torch.float32, device=dev)
         dpf = torch.empty((h.R, 64), dtype=torch.float32, device=dev)
         dmf = torch.empty((h.R, 64), dtype=torch.float32, device=dev)
         ng = lib.query('strive_gnn_param_count', C.byref(h.dec.struct.gnn))
@@ -856,12 +856,12 @@ def _decoder_variant(pack):
 def _decoder_pack_key(model, map_env, dev):
     key = ('dec', str(dev), map_env.nusc_raster.data_ptr())
     # plain values the pack copies: normaliser statistics and the bicycle parameters (not object identities)
-    # (a direct-output model -- output_bicycle=False -- has none; the output mode is part of the key)
+    # (a direct-output model -- output_bicycle=False -- has none; the output mode and the latent width are part of the key)
     nm, an = model.normalizer, model.att_normalizer
     bp = model.bicycle_params if model.output_bicycle else {}
     extra = (tuple(nm.mean_vals.tolist()), tuple(nm.std_vals.tolist()), tuple(an.mean_vals.tolist()), tuple(an.std_vals.tolist()),
              tuple(sorted((k, tuple(v) if isinstance(v, (tuple, list)) else v) for k, v in bp.items())),
-             tuple(map_env.bounds), map_env.L, map_env.W, bool(model.output_bicycle))
+             tuple(map_env.bounds), map_env.L, map_env.W, bool(model.output_bicycle), int(model.z_size))
     return key, extra
 
 
@@ -962,6 +962,9 @@ def _rollout_context(model, g, map_feat, past_feat, z, map_idx, map_env, ext_fut
     h.sc = info.pack(NS) if copies == 1 else info.stacked(copies).pack(NS)
     h.R = info.NA * NS * copies
     h.FT = int(FT)
+    h.Z = int(model.z_size)             # latent width: the row stride of z and dz (the library takes it from the decoder pack)
+    if z.shape[-1] != h.Z:
+        raise ValueError('z must have latent_size = %d columns, got %s' % (h.Z, tuple(z.shape)))
     h.past_last = _f32c(g.past[:, -1, :])
     h.lw = _f32c(g.lw)
     h.sem = _f32c(g.sem)
