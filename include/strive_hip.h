@@ -141,8 +141,11 @@ typedef struct StriveMap {
     const float* lwise;      /* (L)  */
     const float* wwise;      /* (Wc) */
     int32_t L, Wc;
-    const uint32_t* raster_px4;   /* optional (M, H, W) copy with the 4 layers of a pixel packed into one little-endian
-                                     word (byte c = layer c), or NULL; lets the fused crop gather 4 layers with ONE load */
+    const uint32_t* raster_px4;   /* (M, H, W) copy with the 4 layers of a pixel packed into one little-endian word (byte c =
+                                     layer c): one load gathers 4 layers.  Optional (NULL) for strive_map_crop_u8 and
+                                     strive_coll_point, which fall back to `raster`; REQUIRED by everything that runs the fused
+                                     crop -> conv1 gather (strive_map_cnn_fwd, _fwd_keep, _bwd, _bench_layer and the rollout
+                                     entry points), which return an error for NULL */
 } StriveMap;
 
 /* Map CNN: 6 x [Conv2d(stride 2, pad 0) -> GroupNorm(1 group) -> ReLU] + Linear(512, 64), default

@@ -1839,6 +1839,12 @@ static int cnn_run(const StriveMap* map, const StriveCNN* cnn, const float* pos,
         strive_set_error("map_cnn: workspace too small (%zu < %zu)", ws_bytes, strive_map_cnn_workspace_bytes(N));
         return -1;
     }
+    // conv1b_kernel<true> gathers the crop from the pixel-interleaved copy and from nothing else: every caller that hands a map
+    // (strive_map_cnn_fwd, _fwd_keep, the recomputing backward, the rollout) is refused here, before any launch
+    if (map && !map->raster_px4) {
+        strive_set_error("map_cnn: StriveMap.raster_px4 is NULL (the fused crop -> conv1 gather reads only the pixel-interleaved raster)");
+        return -1;
+    }
     const int ch = N < cnn_chunk() ? N : cnn_chunk();
     StriveArena ar(ws, ws_bytes);
     float* act[6];
@@ -1963,6 +1969,7 @@ extern "C" int strive_map_cnn_bench_layer(const StriveMap* map, const StriveCNN*
     STRIVE_CHECK_ARG(map && cnn && pos && mapix && feat && ws, "null argument");
     STRIVE_CHECK_ARG(N > 0 && N <= CNN_CHUNK_MAX && layer >= 0 && layer <= 81, "bad layer / N");
     STRIVE_CHECK_ARG(ws_bytes >= strive_map_cnn_workspace_bytes(N), "workspace too small");
+    STRIVE_CHECK_ARG(map->raster_px4, "StriveMap.raster_px4 is NULL (the fused crop -> conv1 gather reads only the pixel-interleaved raster)");
     hipStream_t stream = (hipStream_t)stream_;
     StriveArena ar(ws, ws_bytes);
     float* act[6];

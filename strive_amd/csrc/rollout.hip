@@ -546,6 +546,12 @@ int check_decoder(const StriveDecoder* dec, const StriveScenes* sc, int FT) {
         return -1;
     }
     if (FT < 1 || sc->NA < 0 || sc->NS < 1) { strive_set_error("rollout: bad sizes"); return -1; }
+    // every step after the first runs the fused crop -> conv1 gather, which reads only the pixel-interleaved raster: refused here,
+    // before the first launch of the rollout, not at its second step
+    if (FT > 1 && !dec->map.raster_px4) {
+        strive_set_error("rollout: StriveMap.raster_px4 is NULL (the fused crop -> conv1 gather reads only the pixel-interleaved raster)");
+        return -1;
+    }
     return 0;
 }
 

@@ -78,6 +78,42 @@ def test_product_has_no_cpu_path():
         ops.map_crop(None, torch.zeros((1, 4)), torch.zeros((1,), dtype=torch.long))
 
 
+def test_fused_conv1_entry_points_refuse_a_map_without_the_interleaved_raster():
+    """conv1b_kernel<true> gathers from StriveMap.raster_px4 and from nothing else: every entry point that launches it returns an
+    error for NULL before any launch (emulated library: a launch would dereference NULL on the host)."""
+    import sys
+    import torch
+    from strive_amd import params, synth
+    from util import product_model
+    sys.path.insert(0, os.path.join(REPO, 'tests', 'hipemu'))
+    import build as emu_build
+    emu = L.StriveLib(emu_build.build(), require_all=True)
+    raster, dx = synth.make_raster(512, 512)
+    mp = params.pack_map(synth.SyntheticMapEnv(raster, dx), 'cpu')
+    assert mp.struct.raster_px4
+    mp.struct.raster_px4 = None
+    cnn = params.pack_cnn(product_model()[1])
+    n = 2
+    fr = torch.tensor([[60.0, 60.0, 1.0, 0.0], [50.0, 70.0, 0.0, 1.0]])
+    mi = torch.zeros((n,), dtype=torch.int32)
+    z4, o4 = L.f4([0] * 4), L.f4([1] * 4)
+    wsb = emu.query('strive_map_cnn_workspace_bytes', n)
+    ws, feat = torch.zeros(wsb, dtype=torch.uint8), torch.full((n, 64), 7.0)
+    kb = emu.query('strive_map_cnn_keep_bytes', n)
+    kept = torch.zeros(kb, dtype=torch.uint8)
+    npar = emu.query('strive_map_cnn_param_count')
+    bwb = emu.query('strive_map_cnn_bwd_workspace_bytes', n)
+    calls = [('strive_map_cnn_fwd', (mp.ref(), cnn.ref(), L.ptr(fr), z4, o4, L.ptr(mi), n, L.ptr(feat), L.ptr(ws), wsb, None)),
+             ('strive_map_cnn_fwd_keep', (mp.ref(), cnn.ref(), L.ptr(fr), z4, o4, L.ptr(mi), n, L.ptr(feat), L.ptr(ws), wsb, L.ptr(kept), kb, n, 0, None)),
+             ('strive_map_cnn_bench_layer', (mp.ref(), cnn.ref(), 0, L.ptr(fr), z4, o4, L.ptr(mi), n, L.ptr(feat), L.ptr(ws), wsb, None)),
+             ('strive_map_cnn_bwd', (mp.ref(), cnn.ref(), L.ptr(fr), z4, o4, L.ptr(mi), n, L.ptr(torch.ones((n, 64))), L.ptr(torch.zeros(npar)),
+                                     L.ptr(torch.zeros(bwb, dtype=torch.uint8)), bwb, None))]
+    for name, args in calls:
+        with pytest.raises(L.StriveHipError, match='raster_px4'):
+            emu.call(name, *args)
+    assert float(feat.min()) == 7.0 and not bool(ws.any()), 'nothing was launched'
+
+
 def test_product_never_imports_the_oracle():
     import subprocess
     out = subprocess.run(['grep', '-rln', '--include=*.py', '-E', r'^\s*(from|import)\s+oracle', os.path.join(REPO, 'strive_amd')],
