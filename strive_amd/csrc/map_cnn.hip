@@ -20,31 +20,8 @@
 // epilogue of the producing convolution, per tile, and added in tile order by the consumer.
 #include "common.h"
 #include "crop_dev.h"
+#include "conv_dev.h"
 #include <type_traits>
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-#define GN_EPS 1e-5
-
-struct GNStats { double sum, sq; };
-
-// Per-sample GroupNorm(1) moments from the producing layer's per-tile partial sums, added in tile order
-// (no atomics anywhere: the CNN is bitwise reproducible run to run, which matters because the rollout
-// re-samples the raster at poses that depend on these features).
-__device__ __forceinline__ void gn_moments(const GNStats* __restrict__ st, int n, int nparts, double count, float& mean,
-                                           float& rstd) {
-    double s = 0.0, q = 0.0;
-    for (int i = 0; i < nparts; ++i) {
-        s += st[(size_t)n * nparts + i].sum;
-        q += st[(size_t)n * nparts + i].sq;
-    }
-    const double m = s / count;
-    double var = q / count - m * m;
-    var = var < 0.0 ? 0.0 : var;
-    mean = (float)m;
-    rstd = (float)(1.0 / sqrt(var + GN_EPS));
-}
 
 // =============================================================================================
 // Layer 1 on the fp16 matrix cores at fp32 accuracy.
@@ -57,7 +34,6 @@ __device__ __forceinline__ void gn_moments(const GNStats* __restrict__ st, int n
 // tile; the 8th window column is padding with zero weights.
 // Workgroup = 4 waves, 32 (x) x 16 (y) output pixels = 32 pixel tiles of 16, 8 per wave.
 // =============================================================================================
-typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
 
 namespace l1b {
 constexpr int CIN = 4, COUT = 16, KS = 7, IH = 256, OH = 125;
@@ -308,64 +284,6 @@ __global__ __launch_bounds__(C1_NT, 4) void conv1b_kernel(StriveMap map, const f
 // front, parked in registers and fed through three rotating LDS buffers, and the fragment reads of step s+1 are
 // interleaved with the matrix work of step s.
 // =============================================================================================
-template <int CIN_, int COUT_, int KS_, int IH_, int OH_, int NPART_IN_, bool OUT_OCT_, int PT_ = 2, int WGS_PER_CU_ = 2,
-          bool ROWS2_ = false, int CBW_ = 1>
-struct BfCfg {
-    static constexpr int CIN = CIN_, COUT = COUT_, KS = KS_, IH = IH_, OH = OH_, NPART_IN = NPART_IN_;
-    static constexpr bool OUT_OCT = OUT_OCT_;
-    static constexpr int PT = PT_;                                  // pixel tiles of 32 per wave
-    static constexpr bool ROWS2 = ROWS2_;                           // pixel tile = 2 rows x 16 columns (small images) instead of 1 x 32
-    static constexpr int TILE_ROWS = ROWS2 ? 2 : 1;
-    static constexpr int WGS_PER_CU = WGS_PER_CU_;                  // residency target (LDS and register budget)
-    static constexpr int NT = 256, NW = 4, TH = NW * PT * TILE_ROWS, TW = ROWS2 ? 16 : 32;
-    // a workgroup computes CBW blocks of 32 output channels from ONE staging of the input tile (the matrix steps of a pass
-    // run once per block): the input is fetched, normalised and split COUT / (32 CBW) times instead of COUT / 32 times
-    static constexpr int CBW = CBW_, COUT_WG = 32 * CBW, CSPLIT = COUT / COUT_WG;
-    static constexpr int PASS_CH = 8, NPASS = CIN / PASS_CH;
-    static constexpr int ITH = 2 * TH + KS - 2, ITW = 2 * TW + KS - 2, HW = (ITW + 1) / 2;
-    static constexpr int HALF_B = HW * 16, ROW_B = 2 * HALF_B, PIECE_B = ITH * ROW_B;
-    static constexpr int NPIECE = 2;                                          // fp16 pieces per value
-    static constexpr int IN_B = (NPIECE * PIECE_B + 255) / 256 * 256;         // weight fragments start 256-byte aligned
-    static constexpr int NKS = (KS * KS + 1) / 2;                            // MFMA steps per pass (two taps each)
-    static constexpr int WSTEP_B = CBW * 2 * 64 * 16;                        // one matrix step: [block][piece][lane][16 B]
-    static constexpr int TILES_X = (OH + TW - 1) / TW, TILES_Y = (OH + TH - 1) / TH;
-    static constexpr int NPART_OUT = TILES_X * TILES_Y * CSPLIT;
-    static constexpr int UNITS = ITH * ITW, UITERS = (UNITS + NT - 1) / NT;
-    static constexpr size_t LDS_BYTES = (size_t)IN_B + 3 * WSTEP_B + (size_t)CIN * 8 + NW * 16 + 16 + COUT_WG * 4;
-    static constexpr size_t WFRAG_BYTES = (size_t)NPASS * NKS * (COUT / 32) * 2048;
-    static_assert(CIN % PASS_CH == 0 && COUT % COUT_WG == 0 && CIN <= NT, "channel tiling");
-    static_assert(LDS_BYTES * WGS_PER_CU <= 160 * 1024, "LDS budget of the residency target");
-    static_assert((KS == 5 && NKS == 13) || (KS == 3 && NKS == 5), "tap orders exist for 5x5 and 3x3 windows");
-    static_assert(WSTEP_B == 16 * 128 * CBW && WSTEP_B / 16 <= NT, "weight step = one 16-byte piece for each of the first 128 CBW threads");
-    // weight steps of a pass requested before its staging; the rest is requested at matrix step W_LATE_AT, when the registers
-    // of the first steps have been handed to LDS.  Three workgroups per CU leave 168 registers per lane: with all 13 steps
-    // parked (52 registers) conv2 spilled 11 of them to scratch -- 92 MB written and 92 MB read back per 512-agent launch
-    // (rocprofv3 WRITE_SIZE / FETCH_SIZE), a sixth of the kernel's HBM traffic.
-    static constexpr int W_UPFRONT = (WGS_PER_CU >= 3 && NKS > 8) ? 7 : NKS, W_LATE_AT = 2;
-};
-
-// v = p0 + p1 up to 2^-24 |v| (p0 = fp16(v) rounded to nearest, p1 = fp16(v - p0)); v is pre-scaled into fp16's range.
-// Two values per conversion (v_cvt_pk_f16_f32 on gfx950, round to nearest even like the scalar form: same bits, 6 instead of 8
-// instructions per pair); the subtraction stays scalar (no packed fp32 arithmetic: DESIGN.md 8.1).
-typedef float split_f32x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 split_f16x2v __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ void split_f16x2(const float v[8], uint4& p0, uint4& p1) {
-    uint32_t h[4], l[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const split_f32x2 v2 = {v[2 * i], v[2 * i + 1]};
-        const split_f16x2v a = __builtin_convertvector(v2, split_f16x2v);
-        const float r0 = v[2 * i] - (float)a[0];            // exact
-        const float r1 = v[2 * i + 1] - (float)a[1];
-        const split_f32x2 r2 = {r0, r1};
-        const split_f16x2v c = __builtin_convertvector(r2, split_f16x2v);
-        __builtin_memcpy(&h[i], &a, 4);
-        __builtin_memcpy(&l[i], &c, 4);
-    }
-    p0 = make_uint4(h[0], h[1], h[2], h[3]);
-    p1 = make_uint4(l[0], l[1], l[2], l[3]);
-}
-
 // TIMING: phase timestamps (s_memtime) of every workgroup summed into `tprof` (measurement hook only)
 // DBG (measurement hook only, results invalid): 1 = no matrix steps, 2 = no output stores, 3 = no input loads, 4 = 1 + 2
 template <class Cfg, bool TIMING = false, int DBG = 0>
@@ -434,52 +352,27 @@ __global__ __launch_bounds__(Cfg::NT, Cfg::WGS_PER_CU) void conv_bf6_kernel(cons
     };
     issue_loads(0);
     const float my_g = tid < CIN ? gn_g[tid] : 0.f, my_b = tid < CIN ? gn_b[tid] : 0.f;   // in flight during the reduction
-    // The epilogue takes the bias from LDS (round 6).  A global load in the epilogue is waited for with vmcnt(0) (the wait-count pass
-    // merges the divergent store blocks conservatively), and on gfx9 stores count in vmcnt too: every bias load waited for the
-    // stores issued before it -- 16 serial store round trips per wave in conv3's epilogue.
-    if (tid < Cfg::COUT_WG) s_bias[tid] = bias[cb * Cfg::COUT_WG + tid];
+    if (tid < Cfg::COUT_WG) s_bias[tid] = bias[cb * Cfg::COUT_WG + tid];                  // (conv_tile_epilogue: bias from LDS)
 
-    // ---- GroupNorm moments of the input sample: the producer's per-tile partial sums, one per lane, reduced in a
-    // fixed (butterfly) order ----
+    // ---- GroupNorm moments of the input sample by wave 0, then scale / shift by one thread per channel (gn_scale_shift's
+    // arithmetic, split so that gamma / beta are in flight during the reduction; every lane of wave 0 forms mean and rstd, as in the
+    // producers: the same instructions as for lane 0 alone) ----
     if (wave == 0) {
-        double ps = 0.0, pq = 0.0;
-        for (int i = lane; i < Cfg::NPART_IN; i += 64) {
-            ps += st_in[(size_t)n * Cfg::NPART_IN + i].sum;
-            pq += st_in[(size_t)n * Cfg::NPART_IN + i].sq;
-        }
-        ps = wave_sum_d(ps);
-        pq = wave_sum_d(pq);
-        if (lane == 0) {
-            const double cnt = (double)CIN * IH * IH;
-            const double mu = ps / cnt;
-            double var = pq / cnt - mu * mu;
-            var = var < 0.0 ? 0.0 : var;
-            s_mr[0] = (float)mu;
-            s_mr[1] = (float)(1.0 / sqrt(var + GN_EPS));
-        }
+        float mean, rstd;
+        gn_moments_wave<Cfg>(st_in, n, lane, mean, rstd);
+        if (lane == 0) { s_mr[0] = mean; s_mr[1] = rstd; }
     }
     __syncthreads();
-    if (tid < CIN) {
-        // xscale = 2^k folded into the affine map: relu(2^k (a x + b)) = 2^k relu(a x + b), exact
-        const float sc = s_mr[1] * my_g;
-        s_gn[2 * tid] = sc * xscale;
-        s_gn[2 * tid + 1] = (my_b - s_mr[0] * sc) * xscale;
-    }
+    if (tid < CIN) gn_affine(s_mr[0], s_mr[1], my_g, my_b, xscale, s_gn + 2 * tid);
     stamp();
 
     constexpr int CBW = Cfg::CBW, NKS = Cfg::NKS;
     f32x16 acc[CBW][PT];
-#pragma unroll
-    for (int c = 0; c < CBW; ++c)
-#pragma unroll
-        for (int i = 0; i < PT; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[c][i][r] = 0.f;
+    conv_zero_acc(acc);
 
-    // this lane's pixel inside a pixel tile (row, column) and the byte offset of its window origin in the wave's first
-    // tile; tile i is 2 * TILE_ROWS * i input rows further
+    // this lane's pixel inside a pixel tile (row, column) and its window origin in the wave's first tile
     const int prow = Cfg::ROWS2 ? (j >> 4) : 0, pcol = Cfg::ROWS2 ? (j & 15) : j;
-    const int lane_base = (2 * (Cfg::TILE_ROWS * PT * wave + prow)) * Cfg::ROW_B + pcol * 16;
+    const unsigned char* in_lane = s_in + (2 * (Cfg::TILE_ROWS * PT * wave + prow)) * Cfg::ROW_B + pcol * 16;
 
     const uint4* wsrc = reinterpret_cast<const uint4*>(wfrag);
     constexpr int WQ = Cfg::WSTEP_B / 16;                         // 128 CBW x 16 B per matrix step
@@ -499,34 +392,17 @@ __global__ __launch_bounds__(Cfg::NT, Cfg::WGS_PER_CU) void conv_bf6_kernel(cons
             for (int t = 0; t < Cfg::W_UPFRONT; ++t) wq[t] = wstep_src(pass, t)[tid];
         }
         __syncthreads();        // s_gn ready (pass 0) / every wave is done with the previous pass's tiles
-        // ---- 8 input channels of the (2TH+KS-2) x (2TW+KS-2) window: GroupNorm + ReLU (pre-scaled), two-piece fp16 split ----
+        // ---- 8 input channels of the (2TH+KS-2) x (2TW+KS-2) window ----
+        {
+            const float4* gn = reinterpret_cast<const float4*>(s_gn + 2 * pass * Cfg::PASS_CH);
+            const float4 g0 = gn[0], g1 = gn[1], g2 = gn[2], g3 = gn[3];
 #pragma unroll
-        for (int k = 0; k < Cfg::UITERS; ++k) {
-            const int idx = tid + k * NT;
-            if (idx < Cfg::UNITS) {
-                const int col = idx % ITW, r = idx / ITW;
-                const int iy = iy0 + r, ix = ix0 + col;
-                float v[8];
-#pragma unroll
-                for (int e = 0; e < 8; ++e) v[e] = 0.f;             // exact zero outside the image
-                if (iy < IH && ix < IH) {
-                    const float4 a = raw[k][0], b = raw[k][1];
-                    const float4* gn = reinterpret_cast<const float4*>(s_gn + 2 * pass * Cfg::PASS_CH);
-                    const float4 g0 = gn[0], g1 = gn[1], g2 = gn[2], g3 = gn[3];
-                    v[0] = fmaxf(fmaf(a.x, g0.x, g0.y), 0.f);
-                    v[1] = fmaxf(fmaf(a.y, g0.z, g0.w), 0.f);
-                    v[2] = fmaxf(fmaf(a.z, g1.x, g1.y), 0.f);
-                    v[3] = fmaxf(fmaf(a.w, g1.z, g1.w), 0.f);
-                    v[4] = fmaxf(fmaf(b.x, g2.x, g2.y), 0.f);
-                    v[5] = fmaxf(fmaf(b.y, g2.z, g2.w), 0.f);
-                    v[6] = fmaxf(fmaf(b.z, g3.x, g3.y), 0.f);
-                    v[7] = fmaxf(fmaf(b.w, g3.z, g3.w), 0.f);
+            for (int k = 0; k < Cfg::UITERS; ++k) {
+                const int idx = tid + k * NT;
+                if (idx < Cfg::UNITS) {
+                    const int col = idx % ITW, r = idx / ITW;
+                    stage_octet<Cfg>(s_in, r, col, iy0 + r < IH && ix0 + col < IH, raw[k][0], raw[k][1], g0, g1, g2, g3);
                 }
-                uint4 p0, p1;
-                split_f16x2(v, p0, p1);
-                unsigned char* dst = s_in + r * Cfg::ROW_B + (col & 1) * Cfg::HALF_B + (col >> 1) * 16;
-                *reinterpret_cast<uint4*>(dst) = p0;
-                *reinterpret_cast<uint4*>(dst + Cfg::PIECE_B) = p1;
             }
         }
         // ---- weight fragments: step t lives in LDS buffer t % 3.  Steps 0 and 1 go straight in; step t is written at the
@@ -540,60 +416,13 @@ __global__ __launch_bounds__(Cfg::NT, Cfg::WGS_PER_CU) void conv_bf6_kernel(cons
         if (pass < 2) stamp();
         if (pass + 1 < Cfg::NPASS) issue_loads(pass + 1);      // consumed after this pass's matrix work
 
-        // Software pipeline over the MFMA steps: while the matrix cores work on step s, the A/B fragments of step
-        // s+1 are read from LDS into the other register set; one barrier per step.
-        f16x8 fa[2][CBW][2], fb[2][PT][2];
-        auto load_frags = [&](int t, int set) {
-            int ky, kx;
-            if (Cfg::KS == 5) {
-                if (t < 10) { ky = t >> 1; kx = (t & 1) + 2 * h; }
-                else { ky = 2 * (t - 10) + h; kx = 4; ky = ky > 4 ? 4 : ky; }     // (row 5 does not exist: zero-weight slot)
-            } else {        // 3x3: steps 0-2 = row t, columns 0 and 2; step 3 = column 1 of rows 0, 1; step 4 = (2, 1) + zero slot
-                if (t < 3) { ky = t; kx = 2 * h; }
-                else if (t == 3) { ky = h; kx = 1; }
-                else { ky = 2; kx = 1; }
-            }
-            const int off = ky * Cfg::ROW_B + (kx & 1) * Cfg::HALF_B + (kx >> 1) * 16;
-            const unsigned char* wb = s_w + (t % 3) * Cfg::WSTEP_B + lane * 16;
-#pragma unroll
-            for (int c = 0; c < CBW; ++c)
-#pragma unroll
-                for (int pl = 0; pl < 2; ++pl) fa[set][c][pl] = *reinterpret_cast<const f16x8*>(wb + (c * 2 + pl) * 1024);
-#pragma unroll
-            for (int i = 0; i < PT; ++i)
-#pragma unroll
-                for (int pl = 0; pl < 2; ++pl)
-                    fb[set][i][pl] = *reinterpret_cast<const f16x8*>(s_in + pl * Cfg::PIECE_B + 2 * Cfg::TILE_ROWS * i * Cfg::ROW_B + lane_base + off);
-        };
-        load_frags(0, 0);
+        // one barrier per matrix step (the weight ring)
+        ConvFrags<Cfg> fr[2];
+        auto wring = [&](int t) { return s_w + (t % 3) * Cfg::WSTEP_B + lane * 16; };
+        fr[0].load(wring(0), in_lane, 0, h);
 #pragma unroll
         for (int s = 0; s < ((DBG == 1 || DBG == 4) ? 0 : NKS); ++s) {
-            const int cur = s & 1;
-            if (s + 1 < NKS) load_frags(s + 1, cur ^ 1);
-            // three products per (channel block, pixel tile) (w1 x0, w0 x1, w0 x0: the small ones first; w1 x1 is below 2^-24
-            // of the leading product); the accumulation chains alternate so that an MFMA never waits for the one issued just
-            // before it
-            constexpr int TA[3] = {1, 0, 0}, TB[3] = {0, 1, 0};
-#pragma unroll
-            for (int term = 0; term < 3; ++term)
-#pragma unroll
-                for (int c = 0; c < CBW; ++c)
-#pragma unroll
-                    for (int i = 0; i < PT; ++i)
-                        acc[c][i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[cur][c][TA[term]], fb[cur][i][TB[term]], acc[c][i], 0, 0, 0);
-            // issue order: one LDS fragment read of step s+1 behind each MFMA of step s (issuing the reads up front stalls
-            // the wave on the LDS queue before the matrix pipe gets any work)
-            if (s + 1 < NKS) {
-                constexpr int NRD = 2 * CBW + 2 * PT, NMF = 3 * PT * CBW;
-#pragma unroll
-                for (int q = 0; q < (NRD < NMF ? NRD : NMF); ++q) {
-                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);     // 1 MFMA
-                    __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);     // 1 DS read
-                }
-                if (NMF > NRD) __builtin_amdgcn_sched_group_barrier(0x008, NMF - NRD, 0);
-                if (NRD > NMF) __builtin_amdgcn_sched_group_barrier(0x100, NRD - NMF, 0);
-            }
-            __builtin_amdgcn_sched_barrier(0);
+            conv_matrix_step<Cfg>(acc, fr[s & 1], fr[(s & 1) ^ 1], s + 1 < NKS, wring(s + 1), in_lane, s + 1, h);
             if (s + 2 < NKS && wmover) reinterpret_cast<uint4*>(s_w + ((s + 2) % 3) * Cfg::WSTEP_B)[tid] = wq[s + 2];
             if (s == Cfg::W_LATE_AT && Cfg::W_UPFRONT < NKS && wmover) {
 #pragma unroll
@@ -604,58 +433,12 @@ __global__ __launch_bounds__(Cfg::NT, Cfg::WGS_PER_CU) void conv_bf6_kernel(cons
         if (pass < 2) stamp();
     }
 
-    // ---- epilogue: D column = lane&31 = pixel, row = (r&3) + 8*(r>>2) + 4*(lane>>5) = channel within the block ----
-    // GroupNorm moments: the 16 outputs of one accumulator tile (one pixel x 16 channels) are summed in fp32, everything above that
-    // in float64.  The fp32 unit is the same set of values in the same order for every tiling of the layer (CBW, PT are per-form
-    // parameters: DESIGN.md 4.10), so the forms differ only in the grouping of float64 additions: 1e-16, i.e. the same fp32 mean and
-    // rstd -- a scene decoded alone and inside a large batch gets the same map features.
     double dsum = 0.0, dsq = 0.0;
-#pragma unroll
-    for (int c = 0; c < CBW; ++c) {
-#pragma unroll
-        for (int i = 0; i < PT; ++i) {
-            const int oy = oy0 + Cfg::TILE_ROWS * (PT * wave + i) + prow, ox = ox0 + pcol;
-            const bool valid = oy < OH && ox < OH;
-            float fsum = 0.f, fsq = 0.f;
-#pragma unroll
-            for (int rg = 0; rg < 4; ++rg) {
-                const int co = (cb * CBW + c) * 32 + 8 * rg + 4 * h;
-                const float4 bv = *reinterpret_cast<const float4*>(s_bias + c * 32 + 8 * rg + 4 * h);
-                float4 v;
-                v.x = fmaf(acc[c][i][4 * rg + 0], unscale, bv.x);     // unscale = 2^-k exactly: one rounding, like acc + bias
-                v.y = fmaf(acc[c][i][4 * rg + 1], unscale, bv.y);
-                v.z = fmaf(acc[c][i][4 * rg + 2], unscale, bv.z);
-                v.w = fmaf(acc[c][i][4 * rg + 3], unscale, bv.w);
-                if (valid) {
-                    if (DBG == 2 || DBG == 4) {
-                        // (no stores)
-                    } else if (Cfg::OUT_OCT) {     // octet-planar, [n][c/8][y][x][c%8]
-                        *reinterpret_cast<float4*>(out + ((((size_t)n * (COUT / 8) + (co >> 3)) * OH + oy) * OH + ox) * 8 + (co & 7)) = v;
-                    } else {                // NCHW
-                        float* o = out + (((size_t)n * COUT + co) * OH + oy) * OH + ox;
-                        o[0] = v.x;
-                        o[(size_t)OH * OH] = v.y;
-                        o[(size_t)2 * OH * OH] = v.z;
-                        o[(size_t)3 * OH * OH] = v.w;
-                    }
-                    fsum += (v.x + v.y) + (v.z + v.w);
-                    fsq = fmaf(v.x, v.x, fmaf(v.y, v.y, fmaf(v.z, v.z, fmaf(v.w, v.w, fsq))));
-                }
-            }
-            dsum += (double)fsum;
-            dsq += (double)fsq;
-        }
-    }
-    const double lsum = wave_sum_d(dsum), lsq = wave_sum_d(dsq);
-    if (lane == 0) { s_red[2 * wave] = lsum; s_red[2 * wave + 1] = lsq; }
+    conv_tile_epilogue<Cfg>(acc, s_bias, unscale, out + ((size_t)n * (COUT / 8) + cb * CBW * 4) * OH * OH * 8,
+                            oy0 + Cfg::TILE_ROWS * PT * wave, ox0, prow, pcol, h, DBG != 2 && DBG != 4, dsum, dsq);
+    conv_wave_stats(dsum, dsq, lane, s_red + 2 * wave);
     __syncthreads();
-    if (tid == 0) {
-        double a = 0.0, b = 0.0;
-        for (int w = 0; w < Cfg::NW; ++w) { a += s_red[2 * w]; b += s_red[2 * w + 1]; }
-        GNStats& o = st_out[(size_t)n * Cfg::NPART_OUT + (by * Cfg::TILES_X + tile_x) * Cfg::CSPLIT + cb];
-        o.sum = a;
-        o.sq = b;
-    }
+    if (tid == 0) conv_publish_stats(s_red, Cfg::NW, st_out[(size_t)n * Cfg::NPART_OUT + (by * Cfg::TILES_X + tile_x) * Cfg::CSPLIT + cb]);
     stamp();
     if (TIMING && tid == 0) {
         // [0] = workgroups, [1 + k] = sum of (stamp k+1 - stamp k): statistics+first loads, staging 0, steps 0,
@@ -667,10 +450,10 @@ __global__ __launch_bounds__(Cfg::NT, Cfg::WGS_PER_CU) void conv_bf6_kernel(cons
 
 // =============================================================================================
 // conv_bf6_kernel with SPECIALISED waves (round 3).  tools/conv_floor_probe.py: the matrix loop of conv2 is 42 % of the kernel,
-// its memory phases the rest, and the two overlap only across the 3 workgroups of a CU.  Here a persistent workgroup of 8 waves
-// (one per CU) splits the roles: waves 4-7 PRODUCE -- they fetch the 8-channel slice of the next (tile, pass) unit, apply
-// GroupNorm + ReLU, split and write it to one of two LDS input buffers -- while waves 0-3 CONSUME the other buffer: the 13 matrix
-// steps of the previous unit (same instruction order as conv_bf6_kernel: the results are bit-identical) and, after a tile's last
+// its memory phases the rest, and the two overlap only across the 3 workgroups of a CU.  Here a persistent workgroup of 16 waves
+// (one per CU) splits the roles: waves 8-15 PRODUCE -- they fetch the 8-channel slice of the next (tile, pass) unit, apply
+// GroupNorm + ReLU, split and write it to one of two LDS input buffers -- while waves 0-7 CONSUME the other buffer: the 13 matrix
+// steps of the previous unit (conv_matrix_step, like conv_bf6_kernel: the results are bit-identical) and, after a tile's last
 // pass, its epilogue.  One barrier per unit.  The whole layer's weight fragments stay in LDS (52 KB for conv2), so the matrix
 // loop has no ring and no barrier of its own.  A workgroup walks a contiguous range of tiles (all tiles of a sample in a row:
 // halo rows come from its own XCD's L2).
@@ -678,10 +461,9 @@ __global__ __launch_bounds__(Cfg::NT, Cfg::WGS_PER_CU) void conv_bf6_kernel(cons
 template <class Cfg>
 struct WsCfg {
     static constexpr int NCONS_W = 8, NT = 1024, NPROD = 512;        // 8 consumer waves (one output row each), 8 producer waves
-    static constexpr int UITERS = (Cfg::UNITS + NPROD - 1) / NPROD;
     static constexpr int W_B = Cfg::NPASS * Cfg::NKS * Cfg::WSTEP_B;
     static constexpr size_t LDS_BYTES = 2 * (size_t)Cfg::IN_B + W_B + 2 * (size_t)Cfg::CIN * 8 + 2 * 8 * 16 + 64 + Cfg::COUT * 4;
-    static_assert(Cfg::CBW == 1 && Cfg::CSPLIT == 1 && Cfg::OUT_OCT && !Cfg::ROWS2 && Cfg::TH == NCONS_W, "built for conv2's shape");
+    static_assert(Cfg::CBW == 1 && Cfg::CSPLIT == 1 && !Cfg::ROWS2 && Cfg::TH == NCONS_W, "built for conv2's shape");
     static_assert(LDS_BYTES <= 160 * 1024, "LDS budget");
 };
 
@@ -689,6 +471,14 @@ struct WsCfg {
 template <class Cfg>
 struct WsUnits {
     int t_begin, nunit;
+    // this workgroup's tiles: a contiguous range of the (sample, tile) list
+    __device__ __forceinline__ WsUnits(int N) {
+        const int total = N * Cfg::TILES_X * Cfg::TILES_Y;
+        const int per = (total + (int)gridDim.x - 1) / (int)gridDim.x;
+        t_begin = (int)blockIdx.x * per;
+        const int t_end = (t_begin + per) < total ? (t_begin + per) : total;
+        nunit = (t_end > t_begin ? t_end - t_begin : 0) * Cfg::NPASS;
+    }
     __device__ __forceinline__ void tile(int u, int& n, int& ty, int& tx, int& pass) const {
         constexpr int TPS = Cfg::TILES_X * Cfg::TILES_Y;
         const int t = t_begin + u / Cfg::NPASS;
@@ -701,40 +491,49 @@ struct WsUnits {
         tx = r / Cfg::TILES_Y;
         ty = r - tx * Cfg::TILES_Y;
     }
+    // the consumers' statistics slots s_red[tile parity][wave][2]: a wave's sums after the epilogue of the tile whose last unit
+    // is u, and (one thread, at least one barrier later) the tile's partial moments
+    template <int NWAVES>
+    __device__ __forceinline__ void wave_stats(int u, double dsum, double dsq, int wave, int lane, double* s_red) const {
+        conv_wave_stats(dsum, dsq, lane, s_red + (((u / Cfg::NPASS) & 1) * NWAVES + wave) * 2);
+    }
+    template <int NWAVES>
+    __device__ __forceinline__ void publish_stats(int u, const double* s_red, GNStats* __restrict__ st_out) const {
+        int n, ty, tx, pass;
+        tile(u, n, ty, tx, pass);
+        conv_publish_stats(s_red + ((u / Cfg::NPASS) & 1) * NWAVES * 2, NWAVES, st_out[(size_t)n * Cfg::NPART_OUT + (ty * Cfg::TILES_X + tx)]);
+    }
 };
 
-// dbg (STRIVE_CONV_WS_DBG, measurement only, results invalid): 1 = consumers skip the matrix steps, 2 = producers skip the staging,
-// 4 = producers skip the input loads, 8 = every unit loads the same (L2-resident) tile, 16 = consumers skip the epilogue.
-// tprof (bench-layer code 81): clock sums of consumer wave 0 (matrix steps, epilogue, barrier wait) and of the first producer wave
-// (request, stage, barrier wait).  What they showed in round 6 (profiles/r06_conv_ws_decomposition.txt): matrix steps alone 115 us,
-// + epilogue 40 (in series with them), producers alone 117 us (memory), all together 190: two pipelines of about the same service
-// time coupled by a barrier per unit -- the sum of the per-unit maxima, not the maximum of the sums.
-// ---- producer waves (8-15): own function = own register allocation (raw prefetch sets; the consumers keep accumulators) ----
-template <class Cfg>
-__device__ __forceinline__ void ws_producer(const float* __restrict__ in, const GNStats* __restrict__ st_in, const float* __restrict__ gn_g,
-                                         const float* __restrict__ gn_b, float xscale, unsigned char* s_in, float* s_gn,
-                                         WsUnits<Cfg> un, int dbg, unsigned long long* __restrict__ tprof) {
-    using W = WsCfg<Cfg>;
+// ---- producer waves of conv_ws_kernel and conv_wsx_kernel: own function = own register allocation (raw prefetch sets; the
+// consumers keep accumulators).  Threads [FIRST, FIRST + NPROD) of the workgroup; a unit is staged over NIV barrier intervals
+// (conv_ws_kernel: 1; conv_wsx_kernel: one per weight sub-unit).  Barriers: (1), interval 0 (unit 0 whole), then NIV per unit.
+// same_tile (timing probe): every unit loads the same (L2-resident) tile.  tprof: clock sums of the first producer thread. ----
+template <class Cfg, int FIRST, int NPROD, int NIV>
+__device__ __forceinline__ void conv_producer(const float* __restrict__ in, const GNStats* __restrict__ st_in, const float* __restrict__ gn_g,
+                                              const float* __restrict__ gn_b, float xscale, unsigned char* s_in, float* s_gn,
+                                              WsUnits<Cfg> un, int dbg, bool same_tile, unsigned long long* __restrict__ tprof) {
     constexpr int CIN = Cfg::CIN, IH = Cfg::IH, TH = Cfg::TH, TW = Cfg::TW, ITW = Cfg::ITW;
+    constexpr int UITERS = (Cfg::UNITS + NPROD - 1) / NPROD;
     long long tp_req = 0, tp_stage = 0, tp_bar = 0;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int ptid = tid - 64 * W::NCONS_W;
+    const int ptid = tid - FIRST;
     const int nunit = un.nunit;
     // Two register sets: the loads of unit u + 1 are requested before unit u is staged, a whole unit ahead of their use.  The loads
     // are UNCONDITIONAL (addresses clamped into the tensor; stage() zeroes what lies outside): with predicated loads the compiler
     // cannot count what is outstanding and waits for ALL of it (s_waitcnt vmcnt(0)) before staging, i.e. also for the loads it
     // has just issued -- the period was then load latency + staging, whatever the prefetch distance.  (A third set, loads two units
     // ahead, changed nothing in round 6: 194 against 193 us.)
-    float4 raw0[W::UITERS][2], raw1[W::UITERS][2];
-    auto issue_loads = [&](int u, float4 (&raw)[W::UITERS][2]) {
+    float4 raw0[UITERS][2], raw1[UITERS][2];
+    auto issue_loads = [&](int u, float4 (&raw)[UITERS][2]) {
         int n, ty, tx, pass;
         un.tile(u, n, ty, tx, pass);
-        const float* in_n = in + (size_t)((dbg & 8) ? 0 : n) * IH * IH * CIN;
-        const int iy0 = (dbg & 8) ? 0 : 2 * ty * TH, ix0 = (dbg & 8) ? 0 : 2 * tx * TW;
+        const float* in_n = in + (size_t)(same_tile ? 0 : n) * IH * IH * CIN;
+        const int iy0 = same_tile ? 0 : 2 * ty * TH, ix0 = same_tile ? 0 : 2 * tx * TW;
 #pragma unroll
-        for (int k = 0; k < W::UITERS; ++k) {
-            int idx = ptid + k * W::NPROD;
+        for (int k = 0; k < UITERS; ++k) {
+            int idx = ptid + k * NPROD;
             idx = idx < Cfg::UNITS ? idx : Cfg::UNITS - 1;
             const int col = idx % ITW, r = idx / ITW;
             int iy = iy0 + r, ix = ix0 + col;
@@ -745,28 +544,8 @@ __device__ __forceinline__ void ws_producer(const float* __restrict__ in, const 
             raw[k][1] = src[1];
         }
     };
-    // GroupNorm scale / shift of sample n into s_gn[n & 1] (first producer wave; fixed butterfly order like conv_bf6_kernel)
-    auto sample_moments = [&](int n) {
-        double ps = 0.0, pq = 0.0;
-        for (int i = lane; i < Cfg::NPART_IN; i += 64) {
-            ps += st_in[(size_t)n * Cfg::NPART_IN + i].sum;
-            pq += st_in[(size_t)n * Cfg::NPART_IN + i].sq;
-        }
-        ps = wave_sum_d(ps);
-        pq = wave_sum_d(pq);
-        const double cnt = (double)CIN * IH * IH;
-        const double mu = ps / cnt;
-        double var = pq / cnt - mu * mu;
-        var = var < 0.0 ? 0.0 : var;
-        const float mean = (float)mu, rstd = (float)(1.0 / sqrt(var + GN_EPS));
-        if (lane < CIN) {
-            const float sc = rstd * gn_g[lane];
-            float* g = s_gn + (n & 1) * CIN * 2;
-            g[2 * lane] = sc * xscale;
-            g[2 * lane + 1] = (gn_b[lane] - mean * sc) * xscale;
-        }
-    };
-    auto stage = [&](int u, const float4 (&raw)[W::UITERS][2]) {   // raw -> GroupNorm + ReLU -> two fp16 pieces -> s_in[u & 1]
+    // interval `chunk` of the staging of unit u (chunk < 0: all of it): raw -> stage_octet -> s_in[u & 1]
+    auto stage = [&](int u, const float4 (&raw)[UITERS][2], int chunk) {
         int n, ty, tx, pass;
         un.tile(u, n, ty, tx, pass);
         const int iy0 = 2 * ty * TH, ix0 = 2 * tx * TW;
@@ -774,59 +553,46 @@ __device__ __forceinline__ void ws_producer(const float* __restrict__ in, const 
         const float4* gn = reinterpret_cast<const float4*>(s_gn + (n & 1) * CIN * 2 + 2 * pass * Cfg::PASS_CH);
         const float4 g0 = gn[0], g1 = gn[1], g2 = gn[2], g3 = gn[3];
 #pragma unroll
-        for (int k = 0; k < W::UITERS; ++k) {
-            const int idx = ptid + k * W::NPROD;
+        for (int k = 0; k < UITERS; ++k) {
+            if (chunk >= 0 && (k * NIV) / UITERS != chunk) continue;
+            const int idx = ptid + k * NPROD;
             if (idx < Cfg::UNITS) {
                 const int col = idx % ITW, r = idx / ITW;
-                const int iy = iy0 + r, ix = ix0 + col;
-                float v[8];
-#pragma unroll
-                for (int e = 0; e < 8; ++e) v[e] = 0.f;             // exact zero outside the image
-                if (iy < IH && ix < IH) {
-                    const float4 a = raw[k][0], b = raw[k][1];
-                    v[0] = fmaxf(fmaf(a.x, g0.x, g0.y), 0.f);
-                    v[1] = fmaxf(fmaf(a.y, g0.z, g0.w), 0.f);
-                    v[2] = fmaxf(fmaf(a.z, g1.x, g1.y), 0.f);
-                    v[3] = fmaxf(fmaf(a.w, g1.z, g1.w), 0.f);
-                    v[4] = fmaxf(fmaf(b.x, g2.x, g2.y), 0.f);
-                    v[5] = fmaxf(fmaf(b.y, g2.z, g2.w), 0.f);
-                    v[6] = fmaxf(fmaf(b.z, g3.x, g3.y), 0.f);
-                    v[7] = fmaxf(fmaf(b.w, g3.z, g3.w), 0.f);
-                }
-                uint4 p0, p1;
-                split_f16x2(v, p0, p1);
-                unsigned char* dst = buf + r * Cfg::ROW_B + (col & 1) * Cfg::HALF_B + (col >> 1) * 16;
-                *reinterpret_cast<uint4*>(dst) = p0;
-                *reinterpret_cast<uint4*>(dst + Cfg::PIECE_B) = p1;
+                stage_octet<Cfg>(buf, r, col, iy0 + r < IH && ix0 + col < IH, raw[k][0], raw[k][1], g0, g1, g2, g3);
             }
         }
     };
-    int cur_sample;
-    auto request = [&](int u, float4 (&raw)[W::UITERS][2]) {       // loads of unit u (+ its sample's scale / shift when it is a new one)
+    int cur_sample = -1;
+    auto request = [&](int u, float4 (&raw)[UITERS][2]) {       // loads of unit u (+ its sample's scale / shift when it is a new one)
         if (u >= nunit) return;
         if (!(dbg & 4)) issue_loads(u, raw);
         int n, ty, tx, pass;
         un.tile(u, n, ty, tx, pass);
         if (n != cur_sample) {                                    // (its slot s_gn[n & 1] was last read while staging sample n - 2)
-            if (wave == W::NCONS_W) sample_moments(n);
+            if (wave == FIRST / 64) gn_scale_shift<Cfg>(st_in, n, gn_g, gn_b, xscale, lane, s_gn + (n & 1) * CIN * 2);
             cur_sample = n;
         }
     };
-    cur_sample = -1;
     request(0, raw0);
     __syncthreads();                                              // (1) weights, bias and the first sample's scale / shift are in LDS
-    auto iteration = [&](int u, float4 (&raw_cur)[W::UITERS][2], float4 (&raw_next)[W::UITERS][2]) {
+    // one barrier interval: the loads of unit us + 1 go out first (interval 0 of the unit), then unit us is staged, chunk by chunk
+    auto interval = [&](int us, float4 (&raw_cur)[UITERS][2], float4 (&raw_next)[UITERS][2], int chunk) {
         const long long t0 = tprof ? clock64() : 0;
-        request(u + 1, raw_next);
+        if (chunk <= 0) request(us + 1, raw_next);
         const long long t1 = tprof ? clock64() : 0;
-        if (u < nunit && !(dbg & 2)) stage(u, raw_cur);
+        if (us < nunit && !(dbg & 2)) stage(us, raw_cur, chunk);
         const long long t2 = tprof ? clock64() : 0;
         __syncthreads();
         if (tprof) { tp_req += t1 - t0; tp_stage += t2 - t1; tp_bar += clock64() - t2; }
     };
-    for (int u = 0; u <= nunit; u += 2) {
-        iteration(u, raw0, raw1);
-        if (u + 1 <= nunit) iteration(u + 1, raw1, raw0);
+    auto unit = [&](int us, float4 (&raw_cur)[UITERS][2], float4 (&raw_next)[UITERS][2]) {
+#pragma unroll
+        for (int c = 0; c < NIV; ++c) interval(us, raw_cur, raw_next, c);
+    };
+    interval(0, raw0, raw1, -1);                                  // interval 0: unit 0 whole
+    for (int us = 1; us <= nunit; us += 2) {                      // (us == nunit: the consumers' last unit, nothing left to stage)
+        unit(us, raw1, raw0);
+        if (us + 1 <= nunit) unit(us + 1, raw0, raw1);
     }
     if (tprof && ptid == 0) {
         atomicAdd(tprof + 4, (unsigned long long)tp_req);
@@ -835,115 +601,54 @@ __device__ __forceinline__ void ws_producer(const float* __restrict__ in, const 
     }
 }
 
+// dbg (STRIVE_CONV_WS_DBG, measurement only, results invalid): 1 = consumers skip the matrix steps, 2 = producers skip the staging,
+// 4 = producers skip the input loads, 8 = every unit loads the same (L2-resident) tile, 16 = consumers skip the epilogue.
+// tprof (bench-layer code 81): clock sums of consumer wave 0 (matrix steps, epilogue, barrier wait) and of the first producer wave
+// (request, stage, barrier wait).  What they showed in round 6 (profiles/r06_conv_ws_decomposition.txt): matrix steps alone 115 us,
+// + epilogue 40 (in series with them), producers alone 117 us (memory), all together 190: two pipelines of about the same service
+// time coupled by a barrier per unit -- the sum of the per-unit maxima, not the maximum of the sums.
 // ---- consumer waves (0-7): wave w owns output row w of the 8-row tile ----
 template <class Cfg>
 __device__ __forceinline__ void ws_consumer(const unsigned char* s_in, const unsigned char* s_w, double* s_red, const float* s_bias,
                                          float* __restrict__ out, GNStats* __restrict__ st_out, float unscale, WsUnits<Cfg> un, int dbg,
                                          unsigned long long* __restrict__ tprof) {
+    using W = WsCfg<Cfg>;
     constexpr int COUT = Cfg::COUT, OH = Cfg::OH, TH = Cfg::TH, TW = Cfg::TW, NKS = Cfg::NKS, NPASS = Cfg::NPASS;
     long long tc_mat = 0, tc_epi = 0, tc_bar = 0, tc_mark = 0;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int h = lane >> 5, j = lane & 31;
     const int nunit = un.nunit;
-    f32x16 acc0;
+    f32x16 acc[1][1];
     const int lane_base = (2 * wave) * Cfg::ROW_B + j * 16;
     auto matrix_steps = [&](int u) {
         int n, ty, tx, pass;
         un.tile(u, n, ty, tx, pass);
-        const unsigned char* buf = s_in + (u & 1) * Cfg::IN_B;
-        if (pass == 0) {
+        const unsigned char* in_lane = s_in + (u & 1) * Cfg::IN_B + lane_base;
+        if (pass == 0) conv_zero_acc(acc);
+        ConvFrags<Cfg, 1, 1> fr[2];
+        auto wstep = [&](int t) { return s_w + (size_t)(pass * NKS + t) * Cfg::WSTEP_B + lane * 16; };
+        fr[0].load(wstep(0), in_lane, 0, h);
 #pragma unroll
-            for (int r = 0; r < 16; ++r) acc0[r] = 0.f;
-        }
-        f16x8 fa[2][2], fb[2][2];
-        auto load_frags = [&](int t, int set) {
-            int ky, kx;
-            if (Cfg::KS == 5) {
-                if (t < 10) { ky = t >> 1; kx = (t & 1) + 2 * h; }
-                else { ky = 2 * (t - 10) + h; kx = 4; ky = ky > 4 ? 4 : ky; }
-            } else {
-                if (t < 3) { ky = t; kx = 2 * h; }
-                else if (t == 3) { ky = h; kx = 1; }
-                else { ky = 2; kx = 1; }
-            }
-            const int off = ky * Cfg::ROW_B + (kx & 1) * Cfg::HALF_B + (kx >> 1) * 16;
-            const unsigned char* wb = s_w + (size_t)(pass * NKS + t) * Cfg::WSTEP_B + lane * 16;
-#pragma unroll
-            for (int pl = 0; pl < 2; ++pl) {
-                fa[set][pl] = *reinterpret_cast<const f16x8*>(wb + pl * 1024);
-                fb[set][pl] = *reinterpret_cast<const f16x8*>(buf + pl * Cfg::PIECE_B + lane_base + off);
-            }
-        };
-        load_frags(0, 0);
-#pragma unroll
-        for (int s2 = 0; s2 < NKS; ++s2) {
-            const int cur = s2 & 1;
-            if (s2 + 1 < NKS) load_frags(s2 + 1, cur ^ 1);
-            constexpr int TA[3] = {1, 0, 0}, TB[3] = {0, 1, 0};
-#pragma unroll
-            for (int term = 0; term < 3; ++term)
-                acc0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[cur][TA[term]], fb[cur][TB[term]], acc0, 0, 0, 0);
-            // issue order pinned (round 6): one fragment read of step s+1 behind each matrix instruction of step s.  Left to itself the
-            // scheduler (which does not know that the dynamic LDS allocation admits one workgroup per CU, and so minimises registers)
-            // re-reads each weight fragment into ONE register set just before its use: ds_read, s_waitcnt lgkmcnt(0), two matrix
-            // instructions, ds_read ... -- an exposed LDS round trip per pair of matrix instructions.
-            if (s2 + 1 < NKS) {
-#pragma unroll
-                for (int q = 0; q < 3; ++q) {
-                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                    __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-                }
-                __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-        }
+        for (int s = 0; s < NKS; ++s)
+            conv_matrix_step<Cfg>(acc, fr[s & 1], fr[(s & 1) ^ 1], s + 1 < NKS, wstep(s + 1), in_lane, s + 1, h);
         if (tprof) tc_mark = clock64();
         if (pass + 1 < NPASS || (dbg & 16)) return;
-        // ---- epilogue of the tile: the bias comes from LDS (see conv_bf6_kernel) ----
-        const int oy = ty * TH + wave, ox = tx * TW + j;
-        const bool valid = oy < OH && ox < OH;
-        float fsum = 0.f, fsq = 0.f;
-#pragma unroll
-        for (int rg = 0; rg < 4; ++rg) {
-            const int co = 8 * rg + 4 * h;
-            const float4 bv = *reinterpret_cast<const float4*>(s_bias + co);
-            float4 v;
-            v.x = fmaf(acc0[4 * rg + 0], unscale, bv.x);
-            v.y = fmaf(acc0[4 * rg + 1], unscale, bv.y);
-            v.z = fmaf(acc0[4 * rg + 2], unscale, bv.z);
-            v.w = fmaf(acc0[4 * rg + 3], unscale, bv.w);
-            if (valid) {
-                *reinterpret_cast<float4*>(out + ((((size_t)n * (COUT / 8) + (co >> 3)) * OH + oy) * OH + ox) * 8 + (co & 7)) = v;
-                fsum += (v.x + v.y) + (v.z + v.w);
-                fsq = fmaf(v.x, v.x, fmaf(v.y, v.y, fmaf(v.z, v.z, fmaf(v.w, v.w, fsq))));
-            }
-        }
-        const double lsum = wave_sum_d((double)fsum), lsq = wave_sum_d((double)fsq);
-        const int tl = (u / NPASS) & 1;
-        if (lane == 0) { s_red[(tl * 8 + wave) * 2] = lsum; s_red[(tl * 8 + wave) * 2 + 1] = lsq; }
-    };
-    auto publish_stats = [&](int u) {                              // thread 0, one barrier after the tile's epilogue
-        int n, ty, tx, pass;
-        un.tile(u, n, ty, tx, pass);
-        const int tl = (u / NPASS) & 1;
-        double a = 0.0, b = 0.0;
-        for (int w = 0; w < 8; ++w) { a += s_red[(tl * 8 + w) * 2]; b += s_red[(tl * 8 + w) * 2 + 1]; }
-        GNStats& o = st_out[(size_t)n * Cfg::NPART_OUT + (ty * Cfg::TILES_X + tx)];
-        o.sum = a;
-        o.sq = b;
+        double dsum = 0.0, dsq = 0.0;
+        conv_tile_epilogue<Cfg>(acc, s_bias, unscale, out + (size_t)n * COUT * OH * OH, ty * TH + wave, tx * TW, 0, j, h, true, dsum, dsq);
+        un.template wave_stats<W::NCONS_W>(u, dsum, dsq, wave, lane, s_red);
     };
     __syncthreads();                                              // (1)
     for (int u = 0; u <= nunit; ++u) {
         const long long t0 = tprof ? clock64() : 0;
         tc_mark = t0;
         if (u >= 1 && !(dbg & 1)) matrix_steps(u - 1);
-        if (tid == 0 && u >= 2 && ((u - 2) % NPASS) == NPASS - 1) publish_stats(u - 2);
+        if (tid == 0 && u >= 2 && ((u - 2) % NPASS) == NPASS - 1) un.template publish_stats<W::NCONS_W>(u - 2, s_red, st_out);
         const long long t1 = tprof ? clock64() : 0;
         __syncthreads();
         if (tprof) { tc_mat += tc_mark - t0; tc_epi += t1 - tc_mark; tc_bar += clock64() - t1; }
     }
-    if (tid == 0 && ((nunit - 1) % NPASS) == NPASS - 1) publish_stats(nunit - 1);
+    if (tid == 0 && ((nunit - 1) % NPASS) == NPASS - 1) un.template publish_stats<W::NCONS_W>(nunit - 1, s_red, st_out);
     if (tprof && tid == 0) {
         atomicAdd(tprof + 0, 1ull);
         atomicAdd(tprof + 1, (unsigned long long)tc_mat);
@@ -967,18 +672,13 @@ __global__ __launch_bounds__(1024, 1) void conv_ws_kernel(const float* __restric
     float* s_bias = (float*)(s_red + 2 * 8 * 2) + 16;                       // [COUT]
     const int tid = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    // this workgroup's tiles: a contiguous range of the (sample, tile) list
-    const int total = N * Cfg::TILES_X * Cfg::TILES_Y;
-    const int per = (total + (int)gridDim.x - 1) / (int)gridDim.x;
-    WsUnits<Cfg> un;
-    un.t_begin = (int)blockIdx.x * per;
-    const int t_end = (un.t_begin + per) < total ? (un.t_begin + per) : total;
-    un.nunit = (t_end > un.t_begin ? t_end - un.t_begin : 0) * Cfg::NPASS;
+    const WsUnits<Cfg> un(N);
     for (int i = tid; i < W::W_B / 16; i += W::NT) reinterpret_cast<uint4*>(s_w)[i] = reinterpret_cast<const uint4*>(wfrag)[i];
     if (tid < Cfg::COUT) s_bias[tid] = bias[tid];
     if (un.nunit == 0) return;
     // both roles execute the same sequence of barriers: (1), then one per unit
-    if (wave >= W::NCONS_W) ws_producer<Cfg>(in, st_in, gn_g, gn_b, xscale, s_in, s_gn, un, dbg, tprof);
+    if (wave >= W::NCONS_W)
+        conv_producer<Cfg, 64 * W::NCONS_W, W::NPROD, 1>(in, st_in, gn_g, gn_b, xscale, s_in, s_gn, un, dbg, (dbg & 8) != 0, tprof);
     else ws_consumer<Cfg>(s_in, s_w, s_red, s_bias, out, st_out, unscale, un, dbg, tprof);
 }
 
@@ -995,6 +695,8 @@ __global__ __launch_bounds__(1024, 1) void conv_ws_kernel(const float* __restric
 //   wave 11     STREAMS the weights: a unit's 13 matrix steps are two SUB-UNITS of 7 + 6 steps (28 + 24 KB of fragments; the 5 steps
 //               of a 3x3 layer are one), loaded into the weight buffer the consumers are not reading.
 // One barrier per sub-unit: none inside the matrix loop, no per-step weight ring.
+// dbg (STRIVE_CONV_WS_DBG, timing probes, results invalid): 1 = no matrix steps, 2 = no staging, 4 = no input loads, 8 = no weight
+// stream, 16 = no epilogue
 // =============================================================================================
 template <class Cfg, int NPW_ = 7>
 struct WxCfg {
@@ -1003,131 +705,11 @@ struct WxCfg {
     static constexpr int SUB_STEPS = (Cfg::NKS + NSUB - 1) / NSUB;             // 7 (13 = 7 + 6) / 5
     static constexpr int WSUB_B = SUB_STEPS * Cfg::WSTEP_B;
     static constexpr int WCHUNKS = WSUB_B / 1024;                              // 1 KB (64 lanes x 16 B) pieces of a sub-unit
-    static constexpr int UITERS = (Cfg::UNITS + NPROD - 1) / NPROD;
     static constexpr size_t LDS_BYTES = 2 * (size_t)Cfg::IN_B + 2 * (size_t)WSUB_B + 2 * (size_t)Cfg::CIN * 8 + 2 * GW * 16 + Cfg::COUT * 4 + 64;
-    static_assert(Cfg::CSPLIT == 1 && Cfg::OUT_OCT && Cfg::NW == 4, "one workgroup computes all output channels of its tile");
+    static_assert(Cfg::CSPLIT == 1 && Cfg::NW == 4, "one workgroup computes all output channels of its tile");
     static_assert(LDS_BYTES <= 160 * 1024, "LDS budget");
     static_assert(NT <= 1024, "waves");
 };
-
-template <class Cfg, class W>
-__device__ __forceinline__ void wx_producer(const float* __restrict__ in, const GNStats* __restrict__ st_in, const float* __restrict__ gn_g,
-                                         const float* __restrict__ gn_b, float xscale, unsigned char* s_in, float* s_gn, WsUnits<Cfg> un,
-                                         int dbg) {
-    // dbg (STRIVE_CONV_WS_DBG, timing probes, results invalid): 1 = no matrix steps, 2 = no staging, 4 = no input loads, 8 = no weight stream,
-    // 16 = no epilogue
-    constexpr int CIN = Cfg::CIN, IH = Cfg::IH, TH = Cfg::TH, TW = Cfg::TW, ITW = Cfg::ITW;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int ptid = tid - 64 * W::NCW;
-    const int nunit = un.nunit;
-    float4 raw0[W::UITERS][2], raw1[W::UITERS][2];
-    auto issue_loads = [&](int u, float4 (&raw)[W::UITERS][2]) {
-        int n, ty, tx, pass;
-        un.tile(u, n, ty, tx, pass);
-        const float* in_n = in + (size_t)n * IH * IH * CIN;
-        const int iy0 = 2 * ty * TH, ix0 = 2 * tx * TW;
-#pragma unroll
-        for (int k = 0; k < W::UITERS; ++k) {
-            int idx = ptid + k * W::NPROD;
-            idx = idx < Cfg::UNITS ? idx : Cfg::UNITS - 1;
-            const int col = idx % ITW, r = idx / ITW;
-            int iy = iy0 + r, ix = ix0 + col;
-            iy = iy < IH ? iy : IH - 1;
-            ix = ix < IH ? ix : IH - 1;
-            const float4* src = reinterpret_cast<const float4*>(in_n + (((size_t)pass * IH + iy) * IH + ix) * 8);
-            raw[k][0] = src[0];
-            raw[k][1] = src[1];
-        }
-    };
-    auto sample_moments = [&](int n) {                            // first producer wave; fixed butterfly order like conv_bf6_kernel
-        double ps = 0.0, pq = 0.0;
-        for (int i = lane; i < Cfg::NPART_IN; i += 64) {
-            ps += st_in[(size_t)n * Cfg::NPART_IN + i].sum;
-            pq += st_in[(size_t)n * Cfg::NPART_IN + i].sq;
-        }
-        ps = wave_sum_d(ps);
-        pq = wave_sum_d(pq);
-        const double cnt = (double)CIN * IH * IH;
-        const double mu = ps / cnt;
-        double var = pq / cnt - mu * mu;
-        var = var < 0.0 ? 0.0 : var;
-        const float mean = (float)mu, rstd = (float)(1.0 / sqrt(var + GN_EPS));
-        if (lane < CIN) {
-            const float sc = rstd * gn_g[lane];
-            float* g = s_gn + (n & 1) * CIN * 2;
-            g[2 * lane] = sc * xscale;
-            g[2 * lane + 1] = (gn_b[lane] - mean * sc) * xscale;
-        }
-    };
-    // iterations [k0, k1) of the staging of unit u: raw -> GroupNorm + ReLU -> two fp16 pieces -> s_in[u & 1]
-    auto stage = [&](int u, const float4 (&raw)[W::UITERS][2], int chunk) {
-        int n, ty, tx, pass;
-        un.tile(u, n, ty, tx, pass);
-        const int iy0 = 2 * ty * TH, ix0 = 2 * tx * TW;
-        unsigned char* buf = s_in + (u & 1) * Cfg::IN_B;
-        const float4* gn = reinterpret_cast<const float4*>(s_gn + (n & 1) * CIN * 2 + 2 * pass * Cfg::PASS_CH);
-        const float4 g0 = gn[0], g1 = gn[1], g2 = gn[2], g3 = gn[3];
-#pragma unroll
-        for (int k = 0; k < W::UITERS; ++k) {
-            if (chunk >= 0 && (k * W::NSUB) / W::UITERS != chunk) continue;
-            const int idx = ptid + k * W::NPROD;
-            if (idx < Cfg::UNITS) {
-                const int col = idx % ITW, r = idx / ITW;
-                const int iy = iy0 + r, ix = ix0 + col;
-                float v[8];
-#pragma unroll
-                for (int e = 0; e < 8; ++e) v[e] = 0.f;             // exact zero outside the image
-                if (iy < IH && ix < IH) {
-                    const float4 a = raw[k][0], b = raw[k][1];
-                    v[0] = fmaxf(fmaf(a.x, g0.x, g0.y), 0.f);
-                    v[1] = fmaxf(fmaf(a.y, g0.z, g0.w), 0.f);
-                    v[2] = fmaxf(fmaf(a.z, g1.x, g1.y), 0.f);
-                    v[3] = fmaxf(fmaf(a.w, g1.z, g1.w), 0.f);
-                    v[4] = fmaxf(fmaf(b.x, g2.x, g2.y), 0.f);
-                    v[5] = fmaxf(fmaf(b.y, g2.z, g2.w), 0.f);
-                    v[6] = fmaxf(fmaf(b.z, g3.x, g3.y), 0.f);
-                    v[7] = fmaxf(fmaf(b.w, g3.z, g3.w), 0.f);
-                }
-                uint4 p0, p1;
-                split_f16x2(v, p0, p1);
-                unsigned char* dst = buf + r * Cfg::ROW_B + (col & 1) * Cfg::HALF_B + (col >> 1) * 16;
-                *reinterpret_cast<uint4*>(dst) = p0;
-                *reinterpret_cast<uint4*>(dst + Cfg::PIECE_B) = p1;
-            }
-        }
-    };
-    int cur_sample = -1;
-    auto request = [&](int u, float4 (&raw)[W::UITERS][2]) {       // loads of unit u (+ its sample's scale / shift when it is a new one)
-        if (u >= nunit) return;
-        if (!(dbg & 4)) issue_loads(u, raw);
-        int n, ty, tx, pass;
-        un.tile(u, n, ty, tx, pass);
-        if (n != cur_sample) {                                    // (slot s_gn[n & 1] was last read while staging sample n - 2)
-            if (wave == W::NCW) sample_moments(n);
-            cur_sample = n;
-        }
-    };
-    request(0, raw0);
-    __syncthreads();                                              // (1) the first sample's scale / shift
-    // interval 0: unit 0 whole
-    request(1, raw1);
-    if (!(dbg & 2)) stage(0, raw0, -1);
-    __syncthreads();
-    // intervals of unit us - 1 (consumers): stage unit us, chunk by chunk; the loads of unit us + 1 go out first
-    auto unit = [&](int us, float4 (&raw_cur)[W::UITERS][2], float4 (&raw_next)[W::UITERS][2]) {
-#pragma unroll
-        for (int h = 0; h < W::NSUB; ++h) {
-            if (h == 0) request(us + 1, raw_next);
-            if (us < nunit && !(dbg & 2)) stage(us, raw_cur, h);
-            __syncthreads();
-        }
-    };
-    for (int us = 1; us <= nunit; us += 2) {                      // (us == nunit: the consumers' last unit, nothing left to stage)
-        unit(us, raw1, raw0);
-        if (us + 1 <= nunit) unit(us + 1, raw0, raw1);
-    }
-}
 
 template <class Cfg, class W>
 __device__ __forceinline__ void wx_streamer(const uint32_t* __restrict__ wfrag, unsigned char* s_w, WsUnits<Cfg> un, int dbg) {
@@ -1170,146 +752,48 @@ __device__ __forceinline__ void wx_consumer(const unsigned char* s_in, const uns
     const int h = lane >> 5, j = lane & 31;
     const int nunit = un.nunit;
     f32x16 acc[CBW][PT];
-    const int gwave = wave;
     const int prow = Cfg::ROWS2 ? (j >> 4) : 0, pcol = Cfg::ROWS2 ? (j & 15) : j;
-    const int lane_base = (2 * (Cfg::TILE_ROWS * PT * gwave + prow)) * Cfg::ROW_B + pcol * 16;
+    const int lane_base = (2 * (Cfg::TILE_ROWS * PT * wave + prow)) * Cfg::ROW_B + pcol * 16;
 
-    // matrix steps [S0, S1) of unit u: conv_bf6_kernel's step body (same products, same order)
+    // matrix steps [S0, S1) of unit u (sub-unit HS)
     auto matrix_sub = [&](int u, auto HC) {
         constexpr int HS = decltype(HC)::value;
         constexpr int S0 = HS * W::SUB_STEPS, S1 = (S0 + W::SUB_STEPS) < NKS ? (S0 + W::SUB_STEPS) : NKS;
         int n, ty, tx, pass;
         un.tile(u, n, ty, tx, pass);
-        const unsigned char* buf = s_in + (u & 1) * Cfg::IN_B;
+        const unsigned char* in_lane = s_in + (u & 1) * Cfg::IN_B + lane_base;
         const unsigned char* wbuf = s_w + ((u * W::NSUB + HS) & 1) * W::WSUB_B;
-        if (pass == 0 && HS == 0) {
+        if (pass == 0 && HS == 0) conv_zero_acc(acc);
+        ConvFrags<Cfg> fr[2];
+        auto wstep = [&](int t) { return wbuf + (t - S0) * Cfg::WSTEP_B + lane * 16; };
+        fr[0].load(wstep(S0), in_lane, S0, h);
 #pragma unroll
-            for (int c = 0; c < CBW; ++c)
-#pragma unroll
-                for (int i = 0; i < PT; ++i)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) acc[c][i][r] = 0.f;
-        }
-        f16x8 fa[2][CBW][2], fb[2][PT][2];
-        auto load_frags = [&](int t, int set) {
-            int ky, kx;
-            if (Cfg::KS == 5) {
-                if (t < 10) { ky = t >> 1; kx = (t & 1) + 2 * h; }
-                else { ky = 2 * (t - 10) + h; kx = 4; ky = ky > 4 ? 4 : ky; }
-            } else {
-                if (t < 3) { ky = t; kx = 2 * h; }
-                else if (t == 3) { ky = h; kx = 1; }
-                else { ky = 2; kx = 1; }
-            }
-            const int off = ky * Cfg::ROW_B + (kx & 1) * Cfg::HALF_B + (kx >> 1) * 16;
-            const unsigned char* wb = wbuf + (t - S0) * Cfg::WSTEP_B + lane * 16;
-#pragma unroll
-            for (int c = 0; c < CBW; ++c)
-#pragma unroll
-                for (int pl = 0; pl < 2; ++pl) fa[set][c][pl] = *reinterpret_cast<const f16x8*>(wb + (c * 2 + pl) * 1024);
-#pragma unroll
-            for (int i = 0; i < PT; ++i)
-#pragma unroll
-                for (int pl = 0; pl < 2; ++pl)
-                    fb[set][i][pl] = *reinterpret_cast<const f16x8*>(buf + pl * Cfg::PIECE_B + 2 * Cfg::TILE_ROWS * i * Cfg::ROW_B + lane_base + off);
-        };
-        load_frags(S0, 0);
-#pragma unroll
-        for (int s = S0; s < S1; ++s) {
-            const int cur = (s - S0) & 1;
-            if (s + 1 < S1) load_frags(s + 1, cur ^ 1);
-            constexpr int TA[3] = {1, 0, 0}, TB[3] = {0, 1, 0};
-#pragma unroll
-            for (int term = 0; term < 3; ++term)
-#pragma unroll
-                for (int c = 0; c < CBW; ++c)
-#pragma unroll
-                    for (int i = 0; i < PT; ++i)
-                        acc[c][i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[cur][c][TA[term]], fb[cur][i][TB[term]], acc[c][i], 0, 0, 0);
-            if (s + 1 < S1) {
-                constexpr int NRD = 2 * CBW + 2 * PT, NMF = 3 * PT * CBW;
-#pragma unroll
-                for (int q = 0; q < (NRD < NMF ? NRD : NMF); ++q) {
-                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                    __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-                }
-                if (NMF > NRD) __builtin_amdgcn_sched_group_barrier(0x008, NMF - NRD, 0);
-                if (NRD > NMF) __builtin_amdgcn_sched_group_barrier(0x100, NRD - NMF, 0);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-        }
+        for (int s = S0; s < S1; ++s)
+            conv_matrix_step<Cfg>(acc, fr[(s - S0) & 1], fr[((s - S0) & 1) ^ 1], s + 1 < S1, wstep(s + 1), in_lane, s + 1, h);
     };
-    // epilogue of the tile whose last unit is u, accumulator tiles [q0, q1) (q = c PT + i): conv_bf6_kernel's sums in the same order
-    // (per lane: fp32 over the 16 values of an accumulator tile, float64 above).  All bias values of a slice come from LDS up front,
-    // addresses are a uniform 64-bit sample base + a 32-bit lane offset.  After the last slice: wave sums -> s_red.
-    double dsum = 0.0, dsq = 0.0;
-    auto epilogue = [&](int u, int q0, int q1) {
+    // epilogue of the tile whose last unit is u
+    auto epilogue = [&](int u) {
         int n, ty, tx, pass;
         un.tile(u, n, ty, tx, pass);
-        const int oy0 = ty * TH, ox0 = tx * TW;
-        float* out_n = out + (size_t)n * COUT * OH * OH;                  // [c/8][y][x][c%8]
-        constexpr int PLANE = OH * OH * 8;
-        if (q0 == 0) { dsum = 0.0; dsq = 0.0; }
-#pragma unroll
-        for (int c = 0; c < CBW; ++c) {
-#pragma unroll
-            for (int i = 0; i < PT; ++i) {
-                if (c * PT + i < q0 || c * PT + i >= q1) continue;
-                float4 bv[4];
-#pragma unroll
-                for (int rg = 0; rg < 4; ++rg) bv[rg] = *reinterpret_cast<const float4*>(s_bias + c * 32 + 8 * rg + 4 * h);
-                const int oy = oy0 + Cfg::TILE_ROWS * (PT * gwave + i) + prow, ox = ox0 + pcol;
-                const bool valid = oy < OH && ox < OH;
-                const int loff = (oy * OH + ox) * 8 + 4 * h;
-                float fsum = 0.f, fsq = 0.f;
-#pragma unroll
-                for (int rg = 0; rg < 4; ++rg) {
-                    float4 v;
-                    v.x = fmaf(acc[c][i][4 * rg + 0], unscale, bv[rg].x);
-                    v.y = fmaf(acc[c][i][4 * rg + 1], unscale, bv[rg].y);
-                    v.z = fmaf(acc[c][i][4 * rg + 2], unscale, bv[rg].z);
-                    v.w = fmaf(acc[c][i][4 * rg + 3], unscale, bv[rg].w);
-                    if (valid) {
-                        if (!(dbg & 64)) *reinterpret_cast<float4*>(out_n + (loff + (c * 4 + rg) * PLANE)) = v;
-                        fsum += (v.x + v.y) + (v.z + v.w);
-                        fsq = fmaf(v.x, v.x, fmaf(v.y, v.y, fmaf(v.z, v.z, fmaf(v.w, v.w, fsq))));
-                    }
-                }
-                dsum += (double)fsum;
-                dsq += (double)fsq;
-            }
-        }
-        if (q1 == CBW * PT) {
-            const double lsum = wave_sum_d(dsum), lsq = wave_sum_d(dsq);
-            const int tl = (u / NPASS) & 1;
-            if (lane == 0) { s_red[(tl * W::GW + gwave) * 2] = lsum; s_red[(tl * W::GW + gwave) * 2 + 1] = lsq; }
-        }
+        double dsum = 0.0, dsq = 0.0;
+        conv_tile_epilogue<Cfg>(acc, s_bias, unscale, out + (size_t)n * COUT * OH * OH, ty * TH + Cfg::TILE_ROWS * PT * wave, tx * TW,
+                                prow, pcol, h, !(dbg & 64), dsum, dsq);
+        un.template wave_stats<W::GW>(u, dsum, dsq, wave, lane, s_red);
     };
-    auto publish_stats = [&](int u) {                              // thread 0, at least one barrier after the tile's last epilogue slice
-        int n, ty, tx, pass;
-        un.tile(u, n, ty, tx, pass);
-        const int tl = (u / NPASS) & 1;
-        double a = 0.0, b = 0.0;
-        for (int w = 0; w < W::GW; ++w) { a += s_red[(tl * W::GW + w) * 2]; b += s_red[(tl * W::GW + w) * 2 + 1]; }
-        GNStats& o = st_out[(size_t)n * Cfg::NPART_OUT + (ty * Cfg::TILES_X + tx)];
-        o.sum = a;
-        o.sq = b;
-    };
-    constexpr int NQ = CBW * PT;
     __syncthreads();                                              // (1)
     __syncthreads();                                              // interval 0: unit 0 staged, sub-unit 0's weights in LDS
     for (int u = 0; u < nunit; ++u) {
         if (!(dbg & 1)) matrix_sub(u, std::integral_constant<int, 0>());
-        if (tid == 0 && u >= 1 && ((u - 1) % NPASS) == NPASS - 1) publish_stats(u - 1);
-        if (W::NSUB == 1 && (u % NPASS) == NPASS - 1 && !(dbg & 16)) epilogue(u, 0, NQ);
+        if (tid == 0 && u >= 1 && ((u - 1) % NPASS) == NPASS - 1) un.template publish_stats<W::GW>(u - 1, s_red, st_out);
+        if (W::NSUB == 1 && (u % NPASS) == NPASS - 1 && !(dbg & 16)) epilogue(u);
         __syncthreads();
         if (W::NSUB == 2) {
             if (!(dbg & 1)) matrix_sub(u, std::integral_constant<int, W::NSUB - 1>());
-            if ((u % NPASS) == NPASS - 1 && !(dbg & 16)) epilogue(u, 0, NQ);
+            if ((u % NPASS) == NPASS - 1 && !(dbg & 16)) epilogue(u);
             __syncthreads();
         }
     }
-    if (tid == 0 && nunit >= 1 && ((nunit - 1) % NPASS) == NPASS - 1) publish_stats(nunit - 1);
+    if (tid == 0 && nunit >= 1 && ((nunit - 1) % NPASS) == NPASS - 1) un.template publish_stats<W::GW>(nunit - 1, s_red, st_out);
 }
 
 template <class Cfg, int NPW = 7>
@@ -1327,17 +811,13 @@ __global__ __launch_bounds__(64 * (Cfg::NW + NPW + 1), 1) void conv_wsx_kernel(c
     float* s_bias = (float*)(s_red + 2 * W::GW * 2);                        // [COUT]
     const int tid = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int total = N * Cfg::TILES_X * Cfg::TILES_Y;
-    const int per = (total + (int)gridDim.x - 1) / (int)gridDim.x;
-    WsUnits<Cfg> un;
-    un.t_begin = (int)blockIdx.x * per;
-    const int t_end = (un.t_begin + per) < total ? (un.t_begin + per) : total;
-    un.nunit = (t_end > un.t_begin ? t_end - un.t_begin : 0) * Cfg::NPASS;
+    const WsUnits<Cfg> un(N);
     if (un.nunit == 0) return;
     if (tid < Cfg::COUT) s_bias[tid] = bias[tid];
     // every role executes the same sequence of barriers: (1), interval 0, then one per sub-unit
     if (wave < W::NCW) wx_consumer<Cfg, W>(s_in, s_w, s_red, s_bias, out, st_out, unscale, un, dbg);
-    else if (wave < W::NCW + W::NPW) wx_producer<Cfg, W>(in, st_in, gn_g, gn_b, xscale, s_in, s_gn, un, dbg);
+    else if (wave < W::NCW + W::NPW)
+        conv_producer<Cfg, 64 * W::NCW, W::NPROD, W::NSUB>(in, st_in, gn_g, gn_b, xscale, s_in, s_gn, un, dbg, false, nullptr);
     else wx_streamer<Cfg, W>(wfrag, s_w, un, dbg);
 }
 
@@ -1478,8 +958,9 @@ __global__ __launch_bounds__(Cfg::NT, 2) void conv_bf6s_kernel(const float* __re
                     const float bet[8] = {q0.y, q0.w, q1.y, q1.w, q2.y, q2.w, q3.y, q3.w};
 #pragma unroll
                     for (int e = 0; e < 8; ++e) {
-                        const float sc = rstd * gam[e];                    // scale / shift exactly as the other conv kernels form them
-                        v[e] = fmaxf(fmaf(x[e], sc * xscale, (bet[e] - mean * sc) * xscale), 0.f);
+                        float ss[2];                                       // scale / shift exactly as the other conv kernels form them
+                        gn_affine(mean, rstd, gam[e], bet[e], xscale, ss);
+                        v[e] = fmaxf(fmaf(x[e], ss[0], ss[1]), 0.f);
                     }
                 }
                 uint4 p0, p1;
@@ -1597,19 +1078,40 @@ __global__ __launch_bounds__(Cfg::NT, 2) void conv_bf6s_kernel(const float* __re
     }
 }
 
-template <class Cfg>
-static int launch_bf6s(const float* in, const GNStats* st_in, const float* g, const float* b, const uint32_t* wfrag,
-                       const float* bias, float* out, GNStats* st_out, int N, float xscale, float wscale, hipStream_t stream) {
-    dim3 grid(((N + Cfg::S - 1) / Cfg::S) * Cfg::CSPLIT);
-    static PerDeviceOnce once;
+// What a layer's kernel reads and writes, built once per layer (conv_io) and handed to whichever launcher runs it
+struct ConvIO {
+    const float* in;            // the previous layer's raw output and per-tile moments, its GroupNorm gamma / beta
+    const GNStats* st_in;
+    const float *gn_g, *gn_b;
+    const uint32_t* wfrag;
+    const float* bias;
+    float* out;
+    GNStats* st_out;
+    float xscale, unscale;      // unscale = 1 / (xscale wscale): the two power-of-two scales undone in the epilogue
+};
+// layer l = 1 .. 5 (conv2 .. conv6) on the six layers' activation / statistics arrays
+static ConvIO conv_io(const StriveCNN* cnn, float* const* act, GNStats* const* st, int l) {
+    const uint32_t* const wfrag[6] = {cnn->w1_frag, cnn->w2_frag, cnn->w3_frag, cnn->w4_frag, cnn->w5_frag, cnn->w6_frag};
+    return {act[l - 1], st[l - 1], cnn->gn_g[l - 1], cnn->gn_b[l - 1], wfrag[l], cnn->b[l], act[l], st[l],
+            cnn->xscale[l], 1.0f / (cnn->xscale[l] * cnn->wscale[l])};
+}
+// One launch of a conv kernel on a layer's record.  `once`: the kernel's dynamic-LDS attribute, set once per device.
+template <class K, class... Extra>
+static void conv_launch(K kernel, PerDeviceOnce& once, dim3 grid, int nt, size_t lds_bytes, const ConvIO& io, int N, hipStream_t stream,
+                        Extra... extra) {
     const int dev = once.device();
     if (!once.is_done(dev)) {
-        hipFuncSetAttribute((const void*)conv_bf6s_kernel<Cfg>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)Cfg::LDS_BYTES);
+        hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
         once.set_done(dev);
     }
-    hipLaunchKernelGGL(conv_bf6s_kernel<Cfg>, grid, dim3(Cfg::NT), Cfg::LDS_BYTES, stream, in, st_in, g, b, wfrag, bias, out,
-                       st_out, N, xscale, 1.0f / (xscale * wscale));
-    return 0;
+    hipLaunchKernelGGL(kernel, grid, dim3(nt), lds_bytes, stream, io.in, io.st_in, io.gn_g, io.gn_b, io.wfrag, io.bias, io.out, io.st_out, N,
+                       io.xscale, io.unscale, extra...);
+}
+
+template <class Cfg>
+static void launch_bf6s(const ConvIO& io, int N, hipStream_t stream) {
+    static PerDeviceOnce once;
+    conv_launch(conv_bf6s_kernel<Cfg>, once, dim3(((N + Cfg::S - 1) / Cfg::S) * Cfg::CSPLIT), Cfg::NT, Cfg::LDS_BYTES, io, N, stream);
 }
 
 typedef BfCfg<16, 32, 5, 125, 61, l1b::NPART, true, 2, 3> Bf2;     // conv2: octet-planar in and out
@@ -1631,16 +1133,13 @@ typedef BfsCfg<128, 128, 6, 2, 32, Bfs5::NPART_OUT, false, 1, 2> Bfs6;  // conv6
 // is faster alone and in the two-stream open loop (17.9 against 18.35 ms) but costs the closed loop 1 ms (22.8 against 21.9 ms;
 // leaving 16 or 32 CUs free changes nothing: profiles/r03_ab_conv_ws_closed_loop.json).
 
-// the specialised-wave form (conv_ws_kernel): one persistent workgroup per CU; option conv_ws = 0 keeps conv_bf6_kernel (A/B)
+// the specialised-wave forms (conv_ws_kernel, conv_wsx_kernel): one persistent workgroup per CU (counted once per device), fewer
+// when there are fewer tiles; options conv_ws = 0 / conv_wsx = 0 keep conv_bf6_kernel (A/B)
 template <class Cfg>
-static int launch_ws(const float* in, const GNStats* st_in, const float* g, const float* b, const uint32_t* wfrag,
-                     const float* bias, float* out, GNStats* st_out, int N, float xscale, float wscale, hipStream_t stream,
-                     unsigned long long* tprof = nullptr) {
-    using W = WsCfg<Cfg>;
+static dim3 persistent_grid(int N) {
     static PerDeviceOnce once;
     const int dev = once.device();
     if (!once.is_done(dev)) {
-        hipFuncSetAttribute((const void*)conv_ws_kernel<Cfg>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)W::LDS_BYTES);
         int v = 0;
         if (!(hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0)) v = 256;
         once.value[dev].store(v, std::memory_order_relaxed);
@@ -1648,50 +1147,42 @@ static int launch_ws(const float* in, const GNStats* st_in, const float* g, cons
     }
     const int ncu = once.value[dev].load(std::memory_order_relaxed);
     const int total = N * Cfg::TILES_X * Cfg::TILES_Y;
-    const int grid = total < ncu ? total : ncu;
-    hipLaunchKernelGGL(conv_ws_kernel<Cfg>, dim3(grid), dim3(W::NT), W::LDS_BYTES, stream, in, st_in, g, b, wfrag, bias, out, st_out, N,
-                       xscale, 1.0f / (xscale * wscale), strive_tuning().conv_ws_dbg, tprof);
-    return 0;
+    return dim3(total < ncu ? total : ncu);
+}
+
+template <class Cfg>
+static void launch_ws(const ConvIO& io, int N, hipStream_t stream, unsigned long long* tprof = nullptr) {
+    using W = WsCfg<Cfg>;
+    static PerDeviceOnce once;
+    conv_launch(conv_ws_kernel<Cfg>, once, persistent_grid<Cfg>(N), W::NT, W::LDS_BYTES, io, N, stream, (int)strive_tuning().conv_ws_dbg, tprof);
 }
 
 template <class Cfg, int NPW = 7>
-static int launch_wsx(const float* in, const GNStats* st_in, const float* g, const float* b, const uint32_t* wfrag,
-                      const float* bias, float* out, GNStats* st_out, int N, float xscale, float wscale, hipStream_t stream) {
+static void launch_wsx(const ConvIO& io, int N, hipStream_t stream) {
     using W = WxCfg<Cfg, NPW>;
     static PerDeviceOnce once;
-    const int dev = once.device();
-    if (!once.is_done(dev)) {
-        hipFuncSetAttribute((const void*)conv_wsx_kernel<Cfg, NPW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)W::LDS_BYTES);
-        int v = 0;
-        if (!(hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0)) v = 256;
-        once.value[dev].store(v, std::memory_order_relaxed);
-        once.set_done(dev);
-    }
-    const int ncu = once.value[dev].load(std::memory_order_relaxed);
-    const int total = N * Cfg::TILES_X * Cfg::TILES_Y;
-    const int grid = total < ncu ? total : ncu;
-    const int dbg = strive_tuning().conv_ws_dbg;
-    hipLaunchKernelGGL((conv_wsx_kernel<Cfg, NPW>), dim3(grid), dim3(W::NT), W::LDS_BYTES, stream, in, st_in, g, b, wfrag, bias, out, st_out, N,
-                       xscale, 1.0f / (xscale * wscale), dbg);
-    return 0;
+    conv_launch(conv_wsx_kernel<Cfg, NPW>, once, persistent_grid<Cfg>(N), W::NT, W::LDS_BYTES, io, N, stream, (int)strive_tuning().conv_ws_dbg);
 }
 
-template <class Cfg>
-static int launch_bf6(const float* in, const GNStats* st_in, const float* g, const float* b, const uint32_t* wfrag,
-                      const float* bias, float* out, GNStats* st_out, int N, float xscale, float wscale, hipStream_t stream) {
-    dim3 grid(Cfg::TILES_X * Cfg::CSPLIT, Cfg::TILES_Y, (N + 7) / 8 * 8);      // z rounded up: see the id -> (sample, tile) map in the kernel
+// TIMING / DBG: the measurement forms of the kernel (strive_map_cnn_bench_layer)
+template <class Cfg, bool TIMING = false, int DBG = 0>
+static void launch_bf6(const ConvIO& io, int N, hipStream_t stream, unsigned long long* tprof = nullptr) {
     static PerDeviceOnce once;
-    const int dev = once.device();
-    if (!once.is_done(dev)) {
-        hipFuncSetAttribute((const void*)conv_bf6_kernel<Cfg>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)Cfg::LDS_BYTES);
-        once.set_done(dev);
-    }
     // (round 5, tools/conv_dephase_probe.py at commit "dephase probe": holding back one of every two co-resident workgroups by a
     // fraction of a staging + matrix period -- by wave slot parity or by id -- changes conv2 / conv3 / conv4 by less than the
     // run-to-run noise, profiles/r05_conv_dephase_probe.txt: the workgroups of a CU do not run in lock step)
-    hipLaunchKernelGGL((conv_bf6_kernel<Cfg>), grid, dim3(Cfg::NT), Cfg::LDS_BYTES, stream, in, st_in, g, b, wfrag, bias, out,
-                       st_out, N, xscale, 1.0f / (xscale * wscale), (unsigned long long*)nullptr);
-    return 0;
+    conv_launch(conv_bf6_kernel<Cfg, TIMING, DBG>, once, dim3(Cfg::TILES_X * Cfg::CSPLIT, Cfg::TILES_Y, (N + 7) / 8 * 8),   // z rounded up: see the id -> (sample, tile) map in the kernel
+                Cfg::NT, Cfg::LDS_BYTES, io, N, stream, tprof);
+}
+// a kernel's compile-time debug code DBG (1 .. 4) chosen at run time: f(std::integral_constant<int, DBG>)
+template <class F>
+static void dispatch_dbg(int dbg, F f) {
+    switch (dbg) {
+        case 1: f(std::integral_constant<int, 1>()); break;
+        case 2: f(std::integral_constant<int, 2>()); break;
+        case 3: f(std::integral_constant<int, 3>()); break;
+        case 4: f(std::integral_constant<int, 4>()); break;
+    }
 }
 
 // per-layer configurations            CIN COUT KS  IH  OH  TH  TW  S  CC NWP NWM NPW MTW NPART_IN
@@ -1890,15 +1381,15 @@ static int cnn_run(const StriveMap* map, const StriveCNN* cnn, const float* pos,
                                (const int32_t*)nullptr, crop + (size_t)n0 * 4 * 256 * 256, cnn->w1_frag, 1.0f / cnn->wscale[0],
                                (const float*)cnn->b[0], act[0], st[0]);
         }
+        ConvIO io[6];
+        for (int l = 1; l < 6; ++l) io[l] = conv_io(cnn, act, st, l);
         // conv2: specialised producer / consumer waves (bit-identical to conv_bf6_kernel; option conv_ws = 0 switches back)
         const bool conv_ws = strive_tuning().conv_ws != 0;
-        if (conv_ws && !cnn->conv2_plain)
-            launch_ws<Bf2>(act[0], st[0], cnn->gn_g[0], cnn->gn_b[0], cnn->w2_frag, cnn->b[1], act[1], st[1], n, cnn->xscale[1], cnn->wscale[1], stream);
-        else
-            launch_bf6<Bf2>(act[0], st[0], cnn->gn_g[0], cnn->gn_b[0], cnn->w2_frag, cnn->b[1], act[1], st[1], n, cnn->xscale[1], cnn->wscale[1], stream);
+        if (conv_ws && !cnn->conv2_plain) launch_ws<Bf2>(io[1], n, stream);
+        else launch_bf6<Bf2>(io[1], n, stream);
         if (!keep_tail_activations && !keep && n <= small_batch) {
-            launch_bf6<Bf3s>(act[1], st[1], cnn->gn_g[1], cnn->gn_b[1], cnn->w3_frag, cnn->b[2], act[2], st[2], n, cnn->xscale[2], cnn->wscale[2], stream);
-            launch_bf6<Bf4s>(act[2], st[2], cnn->gn_g[2], cnn->gn_b[2], cnn->w4_frag, cnn->b[3], act[3], st[3], n, cnn->xscale[3], cnn->wscale[3], stream);
+            launch_bf6<Bf3s>(io[2], n, stream);
+            launch_bf6<Bf4s>(io[3], n, stream);
             launch_cnn_tail(cnn, act[3], st[3], Bf4s::NPART_OUT, feat + (size_t)n0 * 64, n, stream, nullptr, tail_s);
             continue;
         }
@@ -1907,18 +1398,18 @@ static int cnn_run(const StriveMap* map, const StriveCNN* cnn, const float* pos,
         // stream's small kernels)
         const bool conv_wsx = strive_tuning().conv_wsx != 0;
         if (conv_wsx && !cnn->conv2_plain) {
-            launch_wsx<Bf3>(act[1], st[1], cnn->gn_g[1], cnn->gn_b[1], cnn->w3_frag, cnn->b[2], act[2], st[2], n, cnn->xscale[2], cnn->wscale[2], stream);
-            launch_wsx<Bf4>(act[2], st[2], cnn->gn_g[2], cnn->gn_b[2], cnn->w4_frag, cnn->b[3], act[3], st[3], n, cnn->xscale[3], cnn->wscale[3], stream);
+            launch_wsx<Bf3>(io[2], n, stream);
+            launch_wsx<Bf4>(io[3], n, stream);
         } else {
-            launch_bf6<Bf3>(act[1], st[1], cnn->gn_g[1], cnn->gn_b[1], cnn->w3_frag, cnn->b[2], act[2], st[2], n, cnn->xscale[2], cnn->wscale[2], stream);
-            launch_bf6<Bf4>(act[2], st[2], cnn->gn_g[2], cnn->gn_b[2], cnn->w4_frag, cnn->b[3], act[3], st[3], n, cnn->xscale[3], cnn->wscale[3], stream);
+            launch_bf6<Bf3>(io[2], n, stream);
+            launch_bf6<Bf4>(io[3], n, stream);
         }
         if (!keep_tail_activations) {
             launch_cnn_tail(cnn, act[3], st[3], NPARTS[3], feat + (size_t)n0 * 64, n, stream, nullptr, tail_s, keep ? &tk : nullptr);
             continue;
         }
-        launch_bf6s<Bfs5>(act[3], st[3], cnn->gn_g[3], cnn->gn_b[3], cnn->w5_frag, cnn->b[4], act[4], st[4], n, cnn->xscale[4], cnn->wscale[4], stream);
-        launch_bf6s<Bfs6>(act[4], st[4], cnn->gn_g[4], cnn->gn_b[4], cnn->w6_frag, cnn->b[5], act[5], st[5], n, cnn->xscale[5], cnn->wscale[5], stream);
+        launch_bf6s<Bfs5>(io[4], n, stream);
+        launch_bf6s<Bfs6>(io[5], n, stream);
         hipLaunchKernelGGL(fc_kernel, dim3((n + 3) / 4), dim3(256), 0, stream, act[5], st[5], cnn->gn_g[5], cnn->gn_b[5],
                            cnn->fc_wt, cnn->fc_b, feat + (size_t)n0 * 64, n);
     }
@@ -1980,69 +1471,44 @@ extern "C" int strive_map_cnn_bench_layer(const StriveMap* map, const StriveCNN*
     Float4Host m, s;
     memcpy(m.v, pos_mean4_host, 16);
     memcpy(s.v, pos_std4_host, 16);
+    ConvIO io[6];
+    for (int l = 1; l < 6; ++l) io[l] = conv_io(cnn, act, st, l);
     switch (layer) {
         case 0:
             hipLaunchKernelGGL(conv1b_kernel<true>, dim3(l1b::TILES_Y, 1, N), dim3(C1_NT), 0, stream, *map, pos, m, s,
                                mapix, (const uint8_t*)nullptr, cnn->w1_frag, 1.0f / cnn->wscale[0], (const float*)cnn->b[0], act[0], st[0]);
             break;
-        case 21: case 22: {   // phase profile of conv2 / conv3: sums of s_memtime deltas land in `feat` (>= 64 bytes, zeroed here)
+        case 21: case 22:   // phase profile of conv2 / conv3: sums of s_memtime deltas land in `feat` (>= 64 bytes, zeroed here)
             hipMemsetAsync(feat, 0, 64, stream);
-            if (layer == 21) {
-                hipFuncSetAttribute((const void*)conv_bf6_kernel<Bf2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)Bf2::LDS_BYTES);
-                hipLaunchKernelGGL((conv_bf6_kernel<Bf2, true>), dim3(Bf2::TILES_X * Bf2::CSPLIT, Bf2::TILES_Y, (N + 7) / 8 * 8), dim3(Bf2::NT), Bf2::LDS_BYTES,
-                                   stream, act[0], st[0], cnn->gn_g[0], cnn->gn_b[0], cnn->w2_frag, cnn->b[1], act[1], st[1], N,
-                                   cnn->xscale[1], 1.0f / (cnn->xscale[1] * cnn->wscale[1]), reinterpret_cast<unsigned long long*>(feat));
-            } else {
-                hipFuncSetAttribute((const void*)conv_bf6_kernel<Bf3, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)Bf3::LDS_BYTES);
-                hipLaunchKernelGGL((conv_bf6_kernel<Bf3, true>), dim3(Bf3::TILES_X * Bf3::CSPLIT, Bf3::TILES_Y, (N + 7) / 8 * 8), dim3(Bf3::NT), Bf3::LDS_BYTES,
-                                   stream, act[1], st[1], cnn->gn_g[1], cnn->gn_b[1], cnn->w3_frag, cnn->b[2], act[2], st[2], N,
-                                   cnn->xscale[2], 1.0f / (cnn->xscale[2] * cnn->wscale[2]), reinterpret_cast<unsigned long long*>(feat));
-            }
+            if (layer == 21) launch_bf6<Bf2, true>(io[1], N, stream, reinterpret_cast<unsigned long long*>(feat));
+            else launch_bf6<Bf3, true>(io[2], N, stream, reinterpret_cast<unsigned long long*>(feat));
             break;
-        }
-        case 11: case 12: case 13: case 14: {   // timing probes of the layer-0 kernel (results are NOT valid): no gather / no fp64 / 1/3 MFMA
-            dim3 gg(l1b::TILES_Y, 1, N);
-            if (layer == 11) hipLaunchKernelGGL((conv1b_kernel<true, 1>), gg, dim3(C1_NT), 0, stream, *map, pos, m, s, mapix, (const uint8_t*)nullptr, cnn->w1_frag, 1.0f / cnn->wscale[0], (const float*)cnn->b[0], act[0], st[0]);
-            if (layer == 12) hipLaunchKernelGGL((conv1b_kernel<true, 2>), gg, dim3(C1_NT), 0, stream, *map, pos, m, s, mapix, (const uint8_t*)nullptr, cnn->w1_frag, 1.0f / cnn->wscale[0], (const float*)cnn->b[0], act[0], st[0]);
-            if (layer == 14) hipLaunchKernelGGL((conv1b_kernel<true, 4>), gg, dim3(C1_NT), 0, stream, *map, pos, m, s, mapix, (const uint8_t*)nullptr, cnn->w1_frag, 1.0f / cnn->wscale[0], (const float*)cnn->b[0], act[0], st[0]);
-            if (layer == 13) hipLaunchKernelGGL((conv1b_kernel<true, 3>), gg, dim3(C1_NT), 0, stream, *map, pos, m, s, mapix, (const uint8_t*)nullptr, cnn->w1_frag, 1.0f / cnn->wscale[0], (const float*)cnn->b[0], act[0], st[0]);
+        case 11: case 12: case 13: case 14:   // timing probes of the layer-0 kernel (results are NOT valid): no gather / no fp64 / 1/3 MFMA / no stores
+            dispatch_dbg(layer % 10, [&](auto D) {
+                hipLaunchKernelGGL((conv1b_kernel<true, decltype(D)::value>), dim3(l1b::TILES_Y, 1, N), dim3(C1_NT), 0, stream, *map, pos, m, s, mapix,
+                                   (const uint8_t*)nullptr, cnn->w1_frag, 1.0f / cnn->wscale[0], (const float*)cnn->b[0], act[0], st[0]);
+            });
             break;
-        }
-        case 31: case 32: case 33: case 34: case 41: case 42: case 43: case 44: {   // timing probes of conv2 (3x) / conv3 (4x): DBG 1..4, results invalid
-            const int dbg = layer % 10;
-#define STRIVE_DBG_LAUNCH(CFG, D, IN, STI, G, B, W, BIAS, OUT, STO, L)                                                                   \
-    hipFuncSetAttribute((const void*)conv_bf6_kernel<CFG, false, D>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CFG::LDS_BYTES);   \
-    hipLaunchKernelGGL((conv_bf6_kernel<CFG, false, D>), dim3(CFG::TILES_X * CFG::CSPLIT, CFG::TILES_Y, (N + 7) / 8 * 8), dim3(CFG::NT),  \
-                       CFG::LDS_BYTES, stream, IN, STI, G, B, W, BIAS, OUT, STO, N, cnn->xscale[L], 1.0f / (cnn->xscale[L] * cnn->wscale[L]), \
-                       (unsigned long long*)nullptr)
-            if (layer < 40) {
-                if (dbg == 1) { STRIVE_DBG_LAUNCH(Bf2, 1, act[0], st[0], cnn->gn_g[0], cnn->gn_b[0], cnn->w2_frag, cnn->b[1], act[1], st[1], 1); }
-                if (dbg == 2) { STRIVE_DBG_LAUNCH(Bf2, 2, act[0], st[0], cnn->gn_g[0], cnn->gn_b[0], cnn->w2_frag, cnn->b[1], act[1], st[1], 1); }
-                if (dbg == 3) { STRIVE_DBG_LAUNCH(Bf2, 3, act[0], st[0], cnn->gn_g[0], cnn->gn_b[0], cnn->w2_frag, cnn->b[1], act[1], st[1], 1); }
-                if (dbg == 4) { STRIVE_DBG_LAUNCH(Bf2, 4, act[0], st[0], cnn->gn_g[0], cnn->gn_b[0], cnn->w2_frag, cnn->b[1], act[1], st[1], 1); }
-            } else {
-                if (dbg == 1) { STRIVE_DBG_LAUNCH(Bf3, 1, act[1], st[1], cnn->gn_g[1], cnn->gn_b[1], cnn->w3_frag, cnn->b[2], act[2], st[2], 2); }
-                if (dbg == 2) { STRIVE_DBG_LAUNCH(Bf3, 2, act[1], st[1], cnn->gn_g[1], cnn->gn_b[1], cnn->w3_frag, cnn->b[2], act[2], st[2], 2); }
-                if (dbg == 3) { STRIVE_DBG_LAUNCH(Bf3, 3, act[1], st[1], cnn->gn_g[1], cnn->gn_b[1], cnn->w3_frag, cnn->b[2], act[2], st[2], 2); }
-                if (dbg == 4) { STRIVE_DBG_LAUNCH(Bf3, 4, act[1], st[1], cnn->gn_g[1], cnn->gn_b[1], cnn->w3_frag, cnn->b[2], act[2], st[2], 2); }
-            }
-#undef STRIVE_DBG_LAUNCH
+        case 31: case 32: case 33: case 34:   // timing probes of conv2: DBG 1..4, results invalid
+            dispatch_dbg(layer % 10, [&](auto D) { launch_bf6<Bf2, false, decltype(D)::value>(io[1], N, stream); });
             break;
-        }
-        case 1: launch_bf6<Bf2>(act[0], st[0], cnn->gn_g[0], cnn->gn_b[0], cnn->w2_frag, cnn->b[1], act[1], st[1], N, cnn->xscale[1], cnn->wscale[1], stream); break;
-        case 51: launch_ws<Bf2>(act[0], st[0], cnn->gn_g[0], cnn->gn_b[0], cnn->w2_frag, cnn->b[1], act[1], st[1], N, cnn->xscale[1], cnn->wscale[1], stream); break;   // conv2, specialised waves
+        case 41: case 42: case 43: case 44:   // ... of conv3
+            dispatch_dbg(layer % 10, [&](auto D) { launch_bf6<Bf3, false, decltype(D)::value>(io[2], N, stream); });
+            break;
+        case 1: launch_bf6<Bf2>(io[1], N, stream); break;
+        case 51: launch_ws<Bf2>(io[1], N, stream); break;   // conv2, specialised waves
         case 81: {   // phase profile of the specialised-wave conv2: clock sums of consumer wave 0 / the first producer wave land in `feat`
             unsigned long long* tp = reinterpret_cast<unsigned long long*>(feat);
             hipMemsetAsync(tp, 0, 64, stream);
-            launch_ws<Bf2>(act[0], st[0], cnn->gn_g[0], cnn->gn_b[0], cnn->w2_frag, cnn->b[1], act[1], st[1], N, cnn->xscale[1], cnn->wscale[1], stream, tp);
+            launch_ws<Bf2>(io[1], N, stream, tp);
             break;
         }
-        case 52: launch_wsx<Bf3>(act[1], st[1], cnn->gn_g[1], cnn->gn_b[1], cnn->w3_frag, cnn->b[2], act[2], st[2], N, cnn->xscale[2], cnn->wscale[2], stream); break;   // conv3, specialised waves + streamed weights
-        case 53: launch_wsx<Bf4>(act[2], st[2], cnn->gn_g[2], cnn->gn_b[2], cnn->w4_frag, cnn->b[3], act[3], st[3], N, cnn->xscale[3], cnn->wscale[3], stream); break;
-        case 2: launch_bf6<Bf3>(act[1], st[1], cnn->gn_g[1], cnn->gn_b[1], cnn->w3_frag, cnn->b[2], act[2], st[2], N, cnn->xscale[2], cnn->wscale[2], stream); break;
-        case 3: launch_bf6<Bf4>(act[2], st[2], cnn->gn_g[2], cnn->gn_b[2], cnn->w4_frag, cnn->b[3], act[3], st[3], N, cnn->xscale[3], cnn->wscale[3], stream); break;
-        case 4: launch_bf6s<Bfs5>(act[3], st[3], cnn->gn_g[3], cnn->gn_b[3], cnn->w5_frag, cnn->b[4], act[4], st[4], N, cnn->xscale[4], cnn->wscale[4], stream); break;
-        case 5: launch_bf6s<Bfs6>(act[4], st[4], cnn->gn_g[4], cnn->gn_b[4], cnn->w6_frag, cnn->b[5], act[5], st[5], N, cnn->xscale[5], cnn->wscale[5], stream); break;
+        case 52: launch_wsx<Bf3>(io[2], N, stream); break;   // conv3, specialised waves + streamed weights
+        case 53: launch_wsx<Bf4>(io[3], N, stream); break;
+        case 2: launch_bf6<Bf3>(io[2], N, stream); break;
+        case 3: launch_bf6<Bf4>(io[3], N, stream); break;
+        case 4: launch_bf6s<Bfs5>(io[4], N, stream); break;
+        case 5: launch_bf6s<Bfs6>(io[5], N, stream); break;
         case 7: launch_cnn_tail(cnn, act[3], st[3], NPARTS[3], feat, N, stream, nullptr, N <= CNN_TAIL_ONE_SAMPLE ? 1 : 2); break;   // conv5 + conv6 + Linear, fused: the form strive_map_cnn_fwd launches for N samples
         case 27: {  // its phase profile: clock sums land in `ws` beyond the activations conv4 left (results in feat stay valid)
             unsigned long long* tp = reinterpret_cast<unsigned long long*>(act[4]);

@@ -197,8 +197,9 @@ __global__ __launch_bounds__(tail::NT, 1) void cnn_tail_kernel(TailArgs A, unsig
         float v[8];
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-            const float sc = rstd * gam[e];                    // scale / shift exactly as the other conv kernels form them
-            v[e] = fmaxf(fmaf(x[e], sc * A.xs5, (bet[e] - mean * sc) * A.xs5), 0.f);
+            float ss[2];                                       // scale / shift exactly as the other conv kernels form them
+            gn_affine(mean, rstd, gam[e], bet[e], A.xs5, ss);
+            v[e] = fmaxf(fmaf(x[e], ss[0], ss[1]), 0.f);
         }
         uint4 p0, p1;
         split_f16x2(v, p0, p1);
@@ -332,12 +333,7 @@ __global__ __launch_bounds__(tail::NT, 1) void cnn_tail_kernel(TailArgs A, unsig
         a = wave_sum_d(a);
         b = wave_sum_d(b);
         if (lane == 0) {
-            const double cnt = (double)COUT * PPS5;
-            const double m = a / cnt;
-            double var = b / cnt - m * m;
-            var = var < 0.0 ? 0.0 : var;
-            s_mr5[2 * wave] = (float)m;
-            s_mr5[2 * wave + 1] = (float)(1.0 / sqrt(var + GN_EPS));
+            gn_mean_rstd(a, b, (double)COUT * PPS5, s_mr5[2 * wave], s_mr5[2 * wave + 1]);
             if (A.st5 && n0 + wave < N)
                 for (int p = 0; p < A.np5; ++p) {
                     GNStats& o = A.st5[(size_t)(n0 + wave) * A.np5 + p];
@@ -441,12 +437,7 @@ __global__ __launch_bounds__(tail::NT, 1) void cnn_tail_kernel(TailArgs A, unsig
             sa = wave_sum_d(sa);
             sb = wave_sum_d(sb);
             if (lane == 0) {
-                const double cnt = (double)COUT * PPS6;
-                const double m = sa / cnt;
-                double var = sb / cnt - m * m;
-                var = var < 0.0 ? 0.0 : var;
-                s_mr6[2 * wave] = (float)m;
-                s_mr6[2 * wave + 1] = (float)(1.0 / sqrt(var + GN_EPS));
+                gn_mean_rstd(sa, sb, (double)COUT * PPS6, s_mr6[2 * wave], s_mr6[2 * wave + 1]);
                 if (A.st6 && n0 + wave < N)
                     for (int p = 0; p < A.np6; ++p) {
                         GNStats& o = A.st6[(size_t)(n0 + wave) * A.np6 + p];
