@@ -570,6 +570,61 @@ int strive_rollout_bwd_train(const StriveDecoder* dec, const StriveScenes* sc, c
                              const void* tape, size_t tape_bytes, void* ws, size_t ws_bytes, strive_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * GRU trajectory encoders (traj_encoder='gru'; reference src/models/traffic_model.py:93-119, 453-523): past / future encoder =
+ * nn.GRU(in, 128, num_layers=4, batch_first=True) over the T frames of every agent, zero initial state, gate order r, z, n
+ * (n = tanh(W_in x + b_in + r (W_hn h + b_hn)), h' = (1 - z) n + z h), then nn.Linear(128, 64) on the top layer's last state.
+ * ---------------------------------------------------------------------------------------------- */
+#define STRIVE_TGRU_LAYERS 4
+#define STRIVE_TGRU_HID 128
+#define STRIVE_TGRU_MAX_IN 32
+
+/* wih[l] (384, in_l) with in_0 = in_size, in_l = 128 otherwise, whh[l] (384, 128): torch layouts; bih[l], bhh[l] (384).
+ * Matrix-core operands (all required; StriveMLP.wf layout, two fp16 pieces): wih_f[l] / whh_f[l] = fragments of wih[l] * ih_sc[l] /
+ * whh[l] * hh_sc[l] (rows = the 384 gate outputs); wih_bf[l][q] / whh_bf[l][q] = fragments of the TRANSPOSE of gate block q
+ * (rows 128 q .. 128 q + 127 of the matrix, q = r, z, n) times the same scale: rows = the layer's inputs, k = the 128 outputs of the
+ * gate -- the input-gradient products of the backward, one per gate.  wih_bf[0] is not read (no gradient reaches the sequence).
+ * out_w (64, 128), out_b (64): the Linear; out_wf / out_wbf its fragments and those of its transpose, times out_sc.
+ * Scales are powers of two. */
+typedef struct StriveTrajGRU {
+    int32_t in_size;          /* NC + 9, at most STRIVE_TGRU_MAX_IN */
+    int32_t reserved;
+    const float* wih[STRIVE_TGRU_LAYERS];
+    const float* whh[STRIVE_TGRU_LAYERS];
+    const float* bih[STRIVE_TGRU_LAYERS];
+    const float* bhh[STRIVE_TGRU_LAYERS];
+    const void* wih_f[STRIVE_TGRU_LAYERS];
+    const void* whh_f[STRIVE_TGRU_LAYERS];
+    const void* wih_bf[STRIVE_TGRU_LAYERS][3];
+    const void* whh_bf[STRIVE_TGRU_LAYERS][3];
+    float ih_sc[STRIVE_TGRU_LAYERS];
+    float hh_sc[STRIVE_TGRU_LAYERS];
+    const float* out_w;
+    const float* out_b;
+    const void* out_wf;
+    const void* out_wbf;
+    float out_sc;
+} StriveTrajGRU;
+
+/* encode_past / encode_future with traj_encoder='gru' (reference src/models/traffic_model.py:477-486, 513-523) on the assembled
+ * sequence x (NA, T, in_size): feat (NA, 64).  ONE launch runs all T steps and all 4 layers; T is a run-time argument.
+ * T < 1 and in_size > STRIVE_TGRU_MAX_IN are refused. */
+int strive_traj_gru_fwd(const StriveTrajGRU* gru, const float* x, int32_t NA, int32_t T, float* feat, strive_stream_t stream);
+
+/* Training: strive_traj_gru_fwd_keep = strive_traj_gru_fwd (same bytes in feat) that also writes what the backward needs into
+ * `kept` (strive_traj_gru_keep_bytes: the input rows, every layer-step's gates r, z, n, W_hn h + b_hn and new state, and the
+ * backward's own scratch, so `kept` is read AND written by strive_traj_gru_bwd).  strive_traj_gru_bwd: d_feat (NA, 64) ->
+ * d_params (+=), strive_traj_gru_param_count floats in the order of the reference modules' named_parameters(): per layer
+ * weight_ih | weight_hh | bias_ih | bias_hh, then the Linear's weight | bias.  The weight gradients are deferred products over
+ * the rows of all steps (WJobTable), not per-step atomics.  No gradient with respect to x: the reference's graph ends at the
+ * data (src/models/traffic_model.py:465-478). */
+size_t strive_traj_gru_param_count(const StriveTrajGRU* gru);
+size_t strive_traj_gru_keep_bytes(const StriveTrajGRU* gru, int32_t NA, int32_t T);
+int strive_traj_gru_fwd_keep(const StriveTrajGRU* gru, const float* x, int32_t NA, int32_t T, float* feat, void* kept,
+                             size_t kept_bytes, strive_stream_t stream);
+int strive_traj_gru_bwd(const StriveTrajGRU* gru, int32_t NA, int32_t T, void* kept, size_t kept_bytes, const float* d_feat,
+                        float* d_params, strive_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Rule-based lane-following planner (reference src/planners/hardcode_goalcond_nusc.py), the planner that
  * adv_gen_rule_based.cfg attacks in closed loop: src/utils/adv_gen_optim.py:133-139 calls
  * HardcodeNuscPlanner.rollout once per optimisation iteration.  All arithmetic is float64 like the reference's numpy.

@@ -44,6 +44,15 @@ class StriveGRU(C.Structure):
                 ('hh_sc', C.c_float * 3), ('ih_sc', C.c_float * 3)]
 
 
+class StriveTrajGRU(C.Structure):
+    _fields_ = [('in_size', C.c_int32), ('reserved', C.c_int32),
+                ('wih', C.c_void_p * 4), ('whh', C.c_void_p * 4), ('bih', C.c_void_p * 4), ('bhh', C.c_void_p * 4),
+                ('wih_f', C.c_void_p * 4), ('whh_f', C.c_void_p * 4),
+                ('wih_bf', (C.c_void_p * 3) * 4), ('whh_bf', (C.c_void_p * 3) * 4),
+                ('ih_sc', C.c_float * 4), ('hh_sc', C.c_float * 4),
+                ('out_w', C.c_void_p), ('out_b', C.c_void_p), ('out_wf', C.c_void_p), ('out_wbf', C.c_void_p), ('out_sc', C.c_float)]
+
+
 class StriveMap(C.Structure):
     _fields_ = [('raster', C.c_void_p), ('dx', C.c_void_p), ('M', C.c_int32), ('C', C.c_int32),
                 ('H', C.c_int32), ('W', C.c_int32), ('lwise', C.c_void_p), ('wwise', C.c_void_p),
@@ -189,6 +198,11 @@ PROTOTYPES = {
                                           P, P, SZ, P, SZ, P, SZ, P]),
     'strive_rollout_bwd_train_kept': (C.c_int, [C.POINTER(StriveDecoder), C.POINTER(StriveScenes), P, P, P, P, P, I, P, P, P, P, P, P,
                                                 P, P, SZ, P, SZ, P, SZ, P]),
+    'strive_traj_gru_fwd': (C.c_int, [C.POINTER(StriveTrajGRU), P, I, I, P, P]),
+    'strive_traj_gru_param_count': (SZ, [C.POINTER(StriveTrajGRU)]),
+    'strive_traj_gru_keep_bytes': (SZ, [C.POINTER(StriveTrajGRU), I, I]),
+    'strive_traj_gru_fwd_keep': (C.c_int, [C.POINTER(StriveTrajGRU), P, I, I, P, P, SZ, P]),
+    'strive_traj_gru_bwd': (C.c_int, [C.POINTER(StriveTrajGRU), I, I, P, SZ, P, P, P]),
     'strive_bicycle_step': (C.c_int, [C.POINTER(StriveDecoder), P, P, P, P, P, P, P, I, P]),
     'strive_rel_pose': (C.c_int, [P, P, P, P, P, P, I, I, P]),
     'strive_planner_workspace_bytes': (SZ, [C.POINTER(StrivePlanner), I, I]),

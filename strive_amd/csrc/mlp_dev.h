@@ -15,6 +15,9 @@
 #define RPT 4          // rows per thread item
 #define LN_EPS 1e-5f
 
+// logistic gate of the GRU cells (rollout.hip gru_layer_lds, scene_rollout.h, traj_gru.hip)
+__device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
+
 // Scratch for the k-split partial sums of dense_lds (one per kernel: not a template).
 #define KSPLIT_CAP (4 * 192)
 __device__ __forceinline__ float* ksplit_buf() {

@@ -232,7 +232,6 @@ __device__ __forceinline__ void direct_backward(const float* prev, const DirectF
 // GRU helpers (one time step, 3 layers, hidden 64; torch.nn.GRU gate order r,z,n)
 // ---------------------------------------------------------------------------------------------
 #define GLD 192
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
 
 // x: LDS [RB_NODE][xld] (layer input), h: LDS [RB_NODE][64] (layer hidden), gi/gh: LDS [RB_NODE][GLD] scratch.
 // Writes the new hidden into hn [RB_NODE][64]; if gates != null stores (r,z,n,gh_n) at gates[RB_NODE][4*64].

@@ -3,7 +3,7 @@
 Host-side mirror of reference src/models/traffic_model.py: same constructor signature, attributes
 (``FT, PT, dt, NC, z_size, normalizer, att_normalizer, bicycle_params``), methods (``embed``,
 ``decode_embedding``, ``sample_batched``, ``sample``, ``reconstruct``, ``forward``, ``encode_map`` ...)
-and the same 174-tensor ``state_dict`` layout, so the reference's optimisation
+and the same ``state_dict`` layout (174 tensors; 182 with the GRU trajectory encoders), so the reference's optimisation
 drivers and checkpoints work unchanged.  The arithmetic is not torch: every method hands tensors to
 the C ABI (include/strive_hip.h) through strive_amd.ops -- the decoder rollout is ONE call that
 enqueues the whole FT-step kernel sequence, and its backward is an explicit reverse-time sweep that
@@ -16,8 +16,14 @@ and yaw rate, go through the kinematic bicycle model; ``set_bicycle_params`` mus
 
 ``latent_size`` (the drivers' ``--latent_size``) may be any width from 1 to 64; 32 is the shipped one.
 
-Not supported (raise NotImplementedError): ``traj_encoder='gru'``, feature sizes other than 64, latent sizes above 64 and
-non-default map-CNN shapes -- no shipped config uses them (last paragraph).
+Both trajectory encoders of the reference are served: ``traj_encoder='mlp'`` (one MLP over all frames) and ``traj_encoder='gru'``
+(past / future encoder = ``nn.GRU(NC + 9, 128, num_layers=4)`` over the frames + ``nn.Linear(128, 64)``, 18 tensors each under
+``past_encoder`` / ``past_out_layer`` / ``future_encoder`` / ``future_out_layer``; one HIP launch per encoder call, DESIGN.md
+section 4.17).
+
+Not supported (raise NotImplementedError): ``traj_encoder='gru'`` together with ``output_bicycle=False`` (no reference fixture pins
+that combination), feature sizes other than 64, latent sizes above 64 and non-default map-CNN shapes -- no shipped config uses them
+(last paragraph).
 """
 import os
 
@@ -44,8 +50,11 @@ class TrafficModel(nn.Module):
                  conv_stride_list=[2, 2, 2, 2, 2, 2],
                  conv_filter_list=[16, 32, 64, 64, 128, 128]):
         super(TrafficModel, self).__init__()
-        if traj_encoder != 'mlp':
-            raise NotImplementedError("strive_amd implements traj_encoder='mlp' (the only one shipped configs use)")
+        if traj_encoder not in TRAJ_ENCODER_CHOICES:
+            raise NotImplementedError("traj_encoder must be one of %s, got %r" % (TRAJ_ENCODER_CHOICES, traj_encoder))
+        if traj_encoder == 'gru' and not output_bicycle:
+            raise NotImplementedError("strive_amd does not serve traj_encoder='gru' together with output_bicycle=False "
+                                      "(no reference fixture pins that combination)")
         if (list(conv_kernel_list), list(conv_stride_list), list(conv_filter_list), conv_channel_in, map_obs_size_pix) != \
                 ([7, 5, 5, 3, 3, 3], [2] * 6, [16, 32, 64, 64, 128, 128], 4, 256):
             raise NotImplementedError('strive_amd implements the default map CNN (4x256x256 crop, 6 stride-2 convs) only')
@@ -80,12 +89,24 @@ class TrafficModel(nn.Module):
         self.map_feat_out_size = map_feat_size
         self.map_feature = nn.Linear(self.map_feat_in_size, map_feat_size)
 
+        # trajectory encoders (reference :93-119): one MLP over all frames, or a 4-layer GRU over the frames + a Linear
+        # (parameter containers only: the GRU runs as ONE HIP launch, ops.encode_traj_gru)
         self.past_feat_size = past_feat_size
-        self.past_in_size = self.NC + self.PT * (self.state_size + self.att_feat_size + 1)
-        self.past_encoder = MLP([self.past_in_size, 128, 128, 128, past_feat_size])
         self.future_feat_size = future_feat_size
-        self.future_in_size = self.NC + self.FT * (self.state_size + self.att_feat_size + 1)
-        self.future_encoder = MLP([self.future_in_size, 128, 128, 128, future_feat_size])
+        if traj_encoder == 'mlp':
+            self.past_in_size = self.NC + self.PT * (self.state_size + self.att_feat_size + 1)
+            self.past_encoder = MLP([self.past_in_size, 128, 128, 128, past_feat_size])
+            self.future_in_size = self.NC + self.FT * (self.state_size + self.att_feat_size + 1)
+            self.future_encoder = MLP([self.future_in_size, 128, 128, 128, future_feat_size])
+        else:
+            self.past_in_size = self.future_in_size = self.NC + self.state_size + self.att_feat_size + 1
+            if self.past_in_size > 32:
+                raise NotImplementedError('strive_amd GRU trajectory encoders take up to 32 inputs per frame (nclasses <= 23), '
+                                          'got %d' % self.past_in_size)
+            self.past_encoder = nn.GRU(self.past_in_size, 128, 4, batch_first=True)
+            self.past_out_layer = nn.Linear(128, past_feat_size)
+            self.future_encoder = nn.GRU(self.future_in_size, 128, 4, batch_first=True)
+            self.future_out_layer = nn.Linear(128, future_feat_size)
 
         self.z_size = latent_size
         self.prior_net = SceneInteractionNet(past_feat_size + map_feat_size + self.NC, self.NC, 4,
@@ -127,10 +148,14 @@ class TrafficModel(nn.Module):
 
     def encode_past(self, scene_graph):
         """(reference src/models/traffic_model.py:453-486)"""
+        if self.traj_encoder_type == 'gru':
+            return ops.encode_traj_gru(self, 'past', scene_graph, scene_graph.past, scene_graph.past_vis)
         return self._encode_traj(self.past_encoder, scene_graph, scene_graph.past, scene_graph.past_vis)
 
     def encode_future(self, scene_graph):
         """(reference src/models/traffic_model.py:488-523)"""
+        if self.traj_encoder_type == 'gru':
+            return ops.encode_traj_gru(self, 'future', scene_graph, scene_graph.future, scene_graph.future_vis)
         return self._encode_traj(self.future_encoder, scene_graph, scene_graph.future, scene_graph.future_vis)
 
     def _latent_net(self, net, scene_graph, feats):

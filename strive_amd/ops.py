@@ -17,7 +17,7 @@ from . import _lib as L
 from . import params
 from ._lib import StriveHipError
 
-__all__ = ['mlp_forward', 'gnn_forward', 'encode_map', 'encode_traj', 'decoder_rollout', 'map_crop', 'coll_point',
+__all__ = ['mlp_forward', 'gnn_forward', 'encode_map', 'encode_traj', 'encode_traj_gru', 'decoder_rollout', 'map_crop', 'coll_point',
            'veh_coll_penalties', 'scene_info', 'transform2frame']
 
 
@@ -608,6 +608,63 @@ def encode_traj(model, encoder, g, traj, vis):
     att = g.lw.unsqueeze(1).expand(NA, T, 2)
     enc_in = torch.cat([torch.cat([local, att], dim=-1).reshape(NA, -1), g.sem], dim=1)
     return encoder(enc_in.detach())
+
+
+class _TrajGRUFn(torch.autograd.Function):
+    """GRU trajectory encoder with parameter gradients (training path): strive_traj_gru_fwd_keep / strive_traj_gru_bwd."""
+
+    @staticmethod
+    def forward(ctx, x, h, *ps):
+        NA, T, _ = x.shape
+        feat = torch.empty((NA, 64), dtype=torch.float32, device=x.device)
+        kb = h.lib.query('strive_traj_gru_keep_bytes', h.pk.ref(), NA, T)
+        kept = torch.empty((max(int(kb), 1),), dtype=torch.uint8, device=x.device)
+        h.lib.call('strive_traj_gru_fwd_keep', h.pk.ref(), L.ptr(x), NA, T, L.ptr(feat), L.ptr(kept), kept.numel(), _stream(x))
+        ctx.h, ctx.kept, ctx.dims, ctx.ps = h, kept, (NA, T), ps
+        return feat
+
+    @staticmethod
+    def backward(ctx, d_feat):
+        h, (NA, T) = ctx.h, ctx.dims
+        n = h.lib.query('strive_traj_gru_param_count', h.pk.ref())
+        dp, give_back = _grad_target(ctx.ps, n, d_feat.device)
+        h.lib.call('strive_traj_gru_bwd', h.pk.ref(), NA, T, L.ptr(ctx.kept), ctx.kept.numel(), L.ptr(_f32c(d_feat)), L.ptr(dp),
+                   _stream(d_feat))
+        return (None, None) + _grad_return(dp, ctx.ps, give_back)
+
+
+def traj_gru_pack(model, which):
+    """StriveTrajGRU of the 'past' / 'future' encoder, re-packed when one of its 18 tensors changed"""
+    enc, out = getattr(model, which + '_encoder'), getattr(model, which + '_out_layer')
+
+    def build():
+        sd = _sd_of(enc, 'e')
+        sd.update(_sd_of(out, 'o'))
+        return params.pack_traj_gru(sd, 'e', 'o')
+    return _cached_pack(model, 'traj_gru/' + which, (enc, out), build)
+
+
+def encode_traj_gru(model, which, g, traj, vis):
+    """Past / future GRU trajectory encoder (traj_encoder='gru'): per-frame input assembly (torch glue) + ONE HIP launch over all
+    frames and layers.  (reference src/models/traffic_model.py:453-523)  The sequence is data: no gradient flows into it."""
+    NA, T, _ = traj.shape
+    lib = _lib_for(traj)
+    local = _rel_pose_data(g.past[:, -1, :4], traj[:, :, :4])
+    local = torch.cat([local, traj[:, :, 4:]], dim=2)
+    local = torch.where((vis == 0.0).unsqueeze(-1), torch.zeros_like(local), local)
+    x = torch.cat([local, vis.unsqueeze(-1), g.lw.unsqueeze(1).expand(NA, T, 2), g.sem.unsqueeze(1).expand(NA, T, g.sem.shape[1])], dim=-1)
+    x = _f32c(x)
+    pk = traj_gru_pack(model, which)
+    if x.shape[2] != pk.struct.in_size:
+        raise ValueError('GRU trajectory encoder expects %d input features per frame, got %d' % (pk.struct.in_size, x.shape[2]))
+    if _wgrad():
+        h = _RolloutCtx()
+        h.lib, h.pk = lib, pk
+        enc, out = getattr(model, which + '_encoder'), getattr(model, which + '_out_layer')
+        return _TrajGRUFn.apply(x, h, *(list(enc.parameters()) + list(out.parameters())))
+    feat = torch.empty((NA, 64), dtype=torch.float32, device=x.device)
+    lib.call('strive_traj_gru_fwd', pk.ref(), L.ptr(x), NA, T, L.ptr(feat), _stream(x))
+    return feat
 
 
 _lin_tables = {}

@@ -348,6 +348,64 @@ def _fill_gru(s, holder, sd, prefix):
             getattr(s, '%s_sc' % name)[l] = sc
 
 
+def _dense_frag_pair(w, sc, want_f=True, want_bf=True):
+    """(wf, wbf) of the (M, K) matrix ``w`` times ``sc`` (StriveMLP.wf / .wbf layout): one strive_pack_dense launch where the
+    library serves w's device, the torch layout code otherwise (same bytes)."""
+    M, K = w.shape
+    lib = _pack_lib(w)
+    if lib is None:
+        return (dense_fragments(w, sc) if want_f else None), (dense_fragments(w.t().contiguous(), sc) if want_bf else None)
+    wf = torch.empty((((M + 15) // 16) * ((K + 31) // 32) * 512,), dtype=torch.int32, device=w.device) if want_f else None
+    wbf = torch.empty((((K + 15) // 16) * ((M + 31) // 32) * 512,), dtype=torch.int32, device=w.device) if want_bf else None
+    lib.call('strive_pack_dense', L.ptr(w), M, K, sc, None, L.ptr(wf), L.ptr(wbf), L.stream_ptr(w))
+    return wf, wbf
+
+
+TGRU_LAYERS, TGRU_HID, TGRU_MAX_IN = 4, 128, 32
+
+
+def pack_traj_gru(sd, enc_prefix, out_prefix):
+    """StriveTrajGRU of one GRU trajectory encoder: ``<enc_prefix>.{weight,bias}_{ih,hh}_l{0..3}`` (nn.GRU(in, 128, 4)) and
+    ``<out_prefix>.{weight,bias}`` (nn.Linear(128, 64)); reference src/models/traffic_model.py:98-119.  Forward fragments of every
+    384-row matrix, and for the backward the fragments of the transpose of each of its three gate blocks."""
+    p = Packed(L.StriveTrajGRU())
+    s = p.struct
+    ws_ = [_c(sd['%s.weight_%s_l%d' % (enc_prefix, k, l)]) for l in range(TGRU_LAYERS) for k in ('ih', 'hh')]
+    ow = _c(sd[out_prefix + '.weight'])
+    prefetch_absmax(ws_ + [ow])
+    H = TGRU_HID
+    in_size = ws_[0].shape[1]
+    if not 1 <= in_size <= TGRU_MAX_IN:
+        raise NotImplementedError('GRU trajectory encoder %s: input width %d, the HIP kernels take 1 to %d' % (enc_prefix, in_size, TGRU_MAX_IN))
+    s.in_size = in_size
+    for l in range(TGRU_LAYERS):
+        wih, whh = ws_[2 * l], ws_[2 * l + 1]
+        if tuple(wih.shape) != (3 * H, in_size if l == 0 else H) or tuple(whh.shape) != (3 * H, H):
+            raise NotImplementedError('GRU trajectory encoder %s: layer %d is not a hidden-128 GRU layer' % (enc_prefix, l))
+        s.wih[l] = p.hold(wih)
+        s.whh[l] = p.hold(whh)
+        s.bih[l] = p.hold(_c(sd['%s.bias_ih_l%d' % (enc_prefix, l)]))
+        s.bhh[l] = p.hold(_c(sd['%s.bias_hh_l%d' % (enc_prefix, l)]))
+        for name, w in (('ih', wih), ('hh', whh)):
+            sc = _pow2_scale(_checked_absmax(w, 'GRU trajectory encoder'))
+            getattr(s, '%s_sc' % name)[l] = sc
+            getattr(s, 'w%s_f' % name)[l] = p.hold(_dense_frag_pair(w, sc, want_bf=False)[0])
+            if name == 'ih' and l == 0:
+                continue                                          # no gradient reaches the input sequence
+            for q in range(3):
+                getattr(s, 'w%s_bf' % name)[l][q] = p.hold(_dense_frag_pair(w[q * H:(q + 1) * H].contiguous(), sc, want_f=False)[1])
+    if tuple(ow.shape) != (64, H):
+        raise NotImplementedError('GRU trajectory encoder %s: output layer must be Linear(128, 64)' % out_prefix)
+    sc = _pow2_scale(_checked_absmax(ow, 'GRU trajectory encoder'))
+    s.out_w = p.hold(ow)
+    s.out_b = p.hold(_c(sd[out_prefix + '.bias']))
+    s.out_sc = sc
+    wf, wbf = _dense_frag_pair(ow, sc)
+    s.out_wf = p.hold(wf)
+    s.out_wbf = p.hold(wbf)
+    return p
+
+
 def _pow2_scale(bound, target=None):
     """largest power of two S with bound * S <= target (fp16's largest finite value is 65504); inside a lagged_absmax context
     the bound is one step old and the target leaves another factor 2"""
