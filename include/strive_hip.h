@@ -468,6 +468,21 @@ int strive_coll_point_rows(const StriveMap* map, const float* fine, int32_t TO, 
 int strive_rect_iou(const float* box_a, const float* lw_a, const float* box_b, const float* lw_b, int32_t P, double* iou,
                     strive_stream_t stream);
 
+/* Planner evaluation metrics (reference src/eval_planner.py:114-218, compute_metrics) of B scenes in ONE launch, float64:
+ * x`scale` up-sampling of the plan (float64) and of the other agents (fp32; NaN = unobserved) as interp_traj
+ * (reference src/losses/adv_gen_nusc.py:625-644, taps restated in the kernel), the IoU of the ego box against every other
+ * agent at every fine step (hit: IoU > 0.02, NaN frames skipped, :517-565), the earliest hit and the lowest agent index
+ * attaining it (np.amin / np.argmin), coll_idx = int((coll_time * (dt / scale)) / dt) or T-1, the relative speed at impact
+ * and the acceleration series of the pre-crash frames.  The ego is NOT among ``others``.
+ *   plan (B,T,4) float64, others (NR,T,4), ptr (B+1) offsets into others, lw_ego (B,2), lw_others (NR,2)
+ *   out_i (B,5) int32 : did_collide, coll_time (T*scale without a hit), coll_agt, coll_idx, number of acceleration frames
+ *   out_d (B,7) double: coll_vel (NaN without a hit), then (sum, max) of |accel|, forward accel, lateral accel
+ *   status (B) int32  : 0 = written; 1 = the scene has no other agent, 2 = its offsets leave ``others`` (outputs untouched)
+ * A scene's outputs are bit-identical whatever else is in the batch.  T >= 2, scale >= 1. */
+int strive_planner_eval_metrics(const double* plan, const float* others, const int32_t* ptr, const float* lw_ego,
+                                const float* lw_others, int32_t B, int32_t NR, int32_t T, int32_t scale, double dt,
+                                int32_t* out_i, double* out_d, int32_t* status, strive_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Training backward (weight gradients) -- reference src/train_traffic.py:103-131 calls loss.backward() through
  * TrafficModel.forward (src/models/traffic_model.py:178-225).

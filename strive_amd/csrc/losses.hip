@@ -348,7 +348,8 @@ extern "C" int strive_interp_traj_bwd(const float* in, const float* d_out, int32
 // clipped against the four edges of the second (Sutherland-Hodgman, <= 8 vertices) and the areas come from the
 // shoelace formula.  A pair with a NaN in either pose yields NaN (the reference skips such frames).
 // =============================================================================================
-__device__ __forceinline__ void box_corners(const float* b, const float* lw, double cx[4], double cy[4]) {
+template <typename PoseT>
+__device__ __forceinline__ void box_corners(const PoseT* b, const float* lw, double cx[4], double cy[4]) {
     const double hl = 0.5 * (double)lw[0], hw = 0.5 * (double)lw[1];
     const double h = atan2((double)b[3], (double)b[2]);
     const double c = cos(h), s = sin(h);
@@ -369,22 +370,9 @@ __device__ __forceinline__ double poly_area(const double* x, const double* y, in
     return 0.5 * fabs(a);
 }
 
-__global__ __launch_bounds__(256) void rect_iou_kernel(const float* __restrict__ box_a, const float* __restrict__ lw_a,
-                                                         const float* __restrict__ box_b, const float* __restrict__ lw_b, int P,
-                                                         double* __restrict__ iou) {
-    const int p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= P) return;
-    const float* a = box_a + (size_t)p * 4;
-    const float* b = box_b + (size_t)p * 4;
-    bool bad = false;
-    for (int i = 0; i < 4; ++i) bad = bad || (a[i] != a[i]) || (b[i] != b[i]);
-    if (bad) {
-        iou[p] = __longlong_as_double(0x7ff8000000000000ll);
-        return;
-    }
-    double ax[4], ay[4], bx[4], by[4];
-    box_corners(a, lw_a + (size_t)p * 2, ax, ay);
-    box_corners(b, lw_b + (size_t)p * 2, bx, by);
+// IoU of two counter-clockwise quadrilaterals: a is clipped against the four edges of b (shared by rect_iou_kernel and
+// planner_eval_kernel)
+__device__ __forceinline__ double quad_clip_iou(const double ax[4], const double ay[4], const double bx[4], const double by[4]) {
     double px[10], py[10], qx[10], qy[10];
     int n = 4;
     for (int i = 0; i < 4; ++i) { px[i] = ax[i]; py[i] = ay[i]; }
@@ -410,7 +398,26 @@ __global__ __launch_bounds__(256) void rect_iou_kernel(const float* __restrict__
     }
     const double inter = n >= 3 ? poly_area(px, py, n) : 0.0;
     const double uni = poly_area(ax, ay, 4) + poly_area(bx, by, 4) - inter;
-    iou[p] = inter / uni;
+    return inter / uni;
+}
+
+__global__ __launch_bounds__(256) void rect_iou_kernel(const float* __restrict__ box_a, const float* __restrict__ lw_a,
+                                                         const float* __restrict__ box_b, const float* __restrict__ lw_b, int P,
+                                                         double* __restrict__ iou) {
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= P) return;
+    const float* a = box_a + (size_t)p * 4;
+    const float* b = box_b + (size_t)p * 4;
+    bool bad = false;
+    for (int i = 0; i < 4; ++i) bad = bad || (a[i] != a[i]) || (b[i] != b[i]);
+    if (bad) {
+        iou[p] = __longlong_as_double(0x7ff8000000000000ll);
+        return;
+    }
+    double ax[4], ay[4], bx[4], by[4];
+    box_corners(a, lw_a + (size_t)p * 2, ax, ay);
+    box_corners(b, lw_b + (size_t)p * 2, bx, by);
+    iou[p] = quad_clip_iou(ax, ay, bx, by);
 }
 
 extern "C" int strive_rect_iou(const float* box_a, const float* lw_a, const float* box_b, const float* lw_b, int32_t P,
@@ -418,6 +425,161 @@ extern "C" int strive_rect_iou(const float* box_a, const float* lw_a, const floa
     STRIVE_CHECK_ARG(box_a && lw_a && box_b && lw_b && iou, "null argument");
     if (P <= 0) return 0;
     hipLaunchKernelGGL(rect_iou_kernel, dim3((P + 255) / 256), dim3(256), 0, (hipStream_t)stream, box_a, lw_a, box_b, lw_b, P, iou);
+    STRIVE_CHECK_LAUNCH();
+    return 0;
+}
+
+// =============================================================================================
+// Planner evaluation metrics (reference src/eval_planner.py:114-218, compute_metrics) for B scenes in one launch, float64.
+// One workgroup per scene.  The (agent, fine step) pairs are strided over the threads: each up-samples the ego's plan and
+// the agent's future at its fine step (interp_traj, :625-644: half-pixel linear taps, heading renormalised; the plan in
+// float64, the other agents in fp32 as the reference holds them, so a NaN neighbour gives a NaN fine frame), forms the
+// two boxes and their IoU, and a hit (IoU > 0.02, NaN frames skipped) enters the integer key fine_step * n + agent into a
+// shared minimum.  The smallest key IS (coll_time, coll_agt) of check_single_veh_coll + np.amin / np.argmin: the earliest
+// first hit, and among the agents hitting then the lowest index; an integer minimum does not depend on the order of
+// evaluation.  Thread 0 then walks the coarse frames 0 upwards (collision index, relative speed at impact, the three
+// acceleration series), so a scene's outputs do not depend on what else is in the batch.
+//   out_i (B,5): did_collide, coll_time (T*scale without a hit), coll_agt, coll_idx, number of acceleration frames
+//   out_d (B,7): coll_vel (NaN without a hit), then sum and max of |accel|, of the forward and of the lateral acceleration
+//   status (B) : 0; 1 for a scene without other agents, 2 for offsets outside ``others`` (nothing else is written for either)
+// =============================================================================================
+#define PLAN_EVAL_IOU_THRESH 0.02
+
+__global__ __launch_bounds__(256) void planner_eval_kernel(const double* __restrict__ plan, const float* __restrict__ others,
+                                                             const int32_t* __restrict__ ptr, const float* __restrict__ lw_ego,
+                                                             const float* __restrict__ lw_others, int NR, int T, int scale, double dt,
+                                                             int32_t* __restrict__ out_i, double* __restrict__ out_d,
+                                                             int32_t* __restrict__ status) {
+    __shared__ int s_key;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int a0 = ptr[b], n = ptr[b + 1] - a0, TO = T * scale;
+    if (n <= 0 || a0 < 0 || a0 + n > NR) {
+        if (tid == 0) status[b] = n == 0 ? 1 : 2;        // 2: ptr does not lie inside ``others`` (nothing is read)
+        return;
+    }
+    if (tid == 0) {
+        s_key = 0x7fffffff;
+        status[b] = 0;
+    }
+    __syncthreads();
+    const double* pl = plan + (size_t)b * T * 4;
+    const float rs_f = (float)(1.0 / (double)scale);
+    const double rs_d = 1.0 / (double)scale;
+    int best = 0x7fffffff;
+    for (int e = tid; e < n * TO; e += 256) {
+        const int j = e / n, al = e - j * n;            // e IS the key fine_step * n + agent
+        // the other agent's fine frame, fp32 (taps as ATen's area_pixel_compute_source_index evaluates them in the tensor's type)
+        float src = __fsub_rn(__fmul_rn(rs_f, __fadd_rn((float)j, 0.5f)), 0.5f);
+        src = src < 0.f ? 0.f : src;
+        int i0 = (int)src;
+        i0 = i0 > T - 1 ? T - 1 : i0;
+        int i1 = i0 < T - 1 ? i0 + 1 : i0;
+        const float w1 = __fsub_rn(src, (float)i0), w0 = __fsub_rn(1.0f, w1);
+        const float* oa = others + ((size_t)(a0 + al) * T + i0) * 4;
+        const float* ob = others + ((size_t)(a0 + al) * T + i1) * 4;
+        float u[4];
+        for (int c = 0; c < 4; ++c) u[c] = __fadd_rn(__fmul_rn(w0, oa[c]), __fmul_rn(w1, ob[c]));
+        if (u[0] != u[0] || u[1] != u[1] || u[2] != u[2] || u[3] != u[3]) continue;
+        const float nrm = sqrtf(u[2] * u[2] + u[3] * u[3]);
+        u[2] = u[2] / nrm;
+        u[3] = u[3] / nrm;
+        // the ego's fine frame, float64
+        double sd = rs_d * ((double)j + 0.5) - 0.5;
+        sd = sd < 0.0 ? 0.0 : sd;
+        int k0 = (int)sd;
+        k0 = k0 > T - 1 ? T - 1 : k0;
+        const int k1 = k0 < T - 1 ? k0 + 1 : k0;
+        const double v1 = sd - (double)k0, v0 = 1.0 - v1;
+        double g[4];
+        for (int c = 0; c < 4; ++c) g[c] = v0 * pl[k0 * 4 + c] + v1 * pl[k1 * 4 + c];
+        const double gn = sqrt(g[2] * g[2] + g[3] * g[3]);
+        g[2] = g[2] / gn;
+        g[3] = g[3] / gn;
+        double ax[4], ay[4], bx[4], by[4];
+        box_corners(g, lw_ego + (size_t)b * 2, ax, ay);
+        box_corners(u, lw_others + (size_t)(a0 + al) * 2, bx, by);
+        const double iou = quad_clip_iou(ax, ay, bx, by);
+        if (iou > PLAN_EVAL_IOU_THRESH) {
+            best = e;                                   // this thread's keys only grow from here
+            break;
+        }
+    }
+    if (best != 0x7fffffff) atomicMin(&s_key, best);
+    __syncthreads();
+    if (tid != 0) return;
+    const int key = s_key;
+    const bool did = key != 0x7fffffff;
+    const int coll_time = did ? key / n : TO;
+    const int coll_agt = did ? key - coll_time * n : 0;
+    // (sic) the reference's expression, in its order of operations: int((coll_time * interp_dt) / dt)
+    const double interp_dt = dt / (double)scale;
+    int coll_idx = did ? (int)(__dmul_rn((double)coll_time, interp_dt) / dt) : T - 1;
+    coll_idx = coll_idx > T - 1 ? T - 1 : coll_idx;
+    int32_t* oi = out_i + (size_t)b * 5;
+    double* od = out_d + (size_t)b * 7;
+    double coll_vel = __longlong_as_double(0x7ff8000000000000ll);
+    if (did) {
+        const int f1 = coll_idx > 0 ? coll_idx : 1, f0 = f1 - 1;
+        const float* q1 = others + ((size_t)(a0 + coll_agt) * T + f1) * 4;
+        const float* q0 = others + ((size_t)(a0 + coll_agt) * T + f0) * 4;
+        const double rx = (pl[f1 * 4 + 0] - pl[f0 * 4 + 0]) / dt - ((double)q1[0] - (double)q0[0]) / dt;
+        const double ry = (pl[f1 * 4 + 1] - pl[f0 * 4 + 1]) / dt - ((double)q1[1] - (double)q0[1]) / dt;
+        coll_vel = sqrt(rx * rx + ry * ry);
+    }
+    // comfort over the pre-crash frames 0..coll_idx (:176-216): speeds s_i along the unit headings, frame 0 upwards
+    const int m = coll_idx + 1;
+    int cnt = 0;
+    double sum[3] = {0.0, 0.0, 0.0}, mx[3] = {0.0, 0.0, 0.0};
+    if (m > 2) {
+        double s_prev = 0.0, vx_prev = 0.0, vy_prev = 0.0, lx_prev = 0.0, ly_prev = 0.0;
+        for (int i = 0; i + 1 < m; ++i) {
+            const double dx = (pl[(i + 1) * 4 + 0] - pl[i * 4 + 0]) / dt, dy = (pl[(i + 1) * 4 + 1] - pl[i * 4 + 1]) / dt;
+            const double s = sqrt(dx * dx + dy * dy);
+            const double hx = pl[i * 4 + 2], hy = pl[i * 4 + 3];
+            const double hn = sqrt(hx * hx + hy * hy);
+            const double ux = hx / hn, uy = hy / hn;
+            const double vx = s * ux, vy = s * uy;
+            if (i > 0) {
+                const double fwd = fabs((s - s_prev) / dt);
+                const double acx = (vx - vx_prev) / dt, acy = (vy - vy_prev) / dt;
+                const double lat = fabs(acx * lx_prev + acy * ly_prev);
+                const double acc = sqrt(acx * acx + acy * acy);
+                const double v[3] = {acc, fwd, lat};
+                for (int c = 0; c < 3; ++c) {
+                    sum[c] += v[c];
+                    mx[c] = (cnt == 0 || v[c] > mx[c] || v[c] != v[c]) ? v[c] : mx[c];
+                }
+                ++cnt;
+            }
+            s_prev = s; vx_prev = vx; vy_prev = vy;
+            lx_prev = -uy; ly_prev = ux;
+        }
+    }
+    oi[0] = did ? 1 : 0;
+    oi[1] = coll_time;
+    oi[2] = coll_agt;
+    oi[3] = coll_idx;
+    oi[4] = cnt;
+    od[0] = coll_vel;
+    for (int c = 0; c < 3; ++c) {
+        od[1 + 2 * c] = sum[c];
+        od[2 + 2 * c] = mx[c];
+    }
+}
+
+extern "C" int strive_planner_eval_metrics(const double* plan, const float* others, const int32_t* ptr, const float* lw_ego,
+                                           const float* lw_others, int32_t B, int32_t NR, int32_t T, int32_t scale, double dt,
+                                           int32_t* out_i, double* out_d, int32_t* status, strive_stream_t stream) {
+    STRIVE_CHECK_ARG(plan && others && ptr && lw_ego && lw_others && out_i && out_d && status, "null argument");
+    STRIVE_CHECK_ARG(T >= 2, "T must be at least 2");
+    STRIVE_CHECK_ARG(scale >= 1, "bad scale");
+    STRIVE_CHECK_ARG(dt > 0.0, "bad dt");
+    // (the key fine_step * n + agent and the strided loop counter, which runs up to 255 past the last key, are ints)
+    STRIVE_CHECK_ARG(NR >= 0 && (int64_t)(NR > 0 ? NR : 1) * T * scale < 0x7fffffffll - 256,
+                     "NR * T * scale does not fit the collision key");
+    if (B <= 0) return 0;
+    hipLaunchKernelGGL(planner_eval_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, plan, others, ptr, lw_ego, lw_others, NR, T,
+                       scale, dt, out_i, out_d, status);
     STRIVE_CHECK_LAUNCH();
     return 0;
 }

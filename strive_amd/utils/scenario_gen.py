@@ -1,6 +1,10 @@
 """Scenario-generation helpers on the hot path (reference src/utils/scenario_gen.py:19-28)."""
 import torch
 
+# The names strive_amd.dropin lays over the reference's utils/scenario_gen.py.  The metric helpers below are not among them:
+# they pool sums and counts (PooledMetric), while the reference's own tools keep lists under the same names and must keep theirs.
+__all__ = ['detach_embed_info', 'determine_feasibility_nusc', 'prepare_output_dict']
+
 
 def detach_embed_info(embed_info_attached):
     out = {}
@@ -89,3 +93,61 @@ def prepare_output_dict(scene_graph, map_idx, map_env, dt, model, init_fut_traj,
     if attack_bike_params is not None:
         out['attack_bike_prof'] = plain(attack_bike_params)
     return out
+
+
+class PooledMetric(object):
+    """Running total and count of one metric's per-frame values.  The reference keeps every value in a list and prints
+    ``np.mean`` of it; the evaluation kernel hands back per-scene sums and counts, and ``total / count`` is that pooled mean
+    (the mean over all frames of all scenes, not a mean of per-scene means)."""
+    __slots__ = ('total', 'count')
+
+    def __init__(self, total=0.0, count=0):
+        self.total, self.count = float(total), int(count)
+
+    def add(self, total, count):
+        self.total += float(total)
+        self.count += int(count)
+
+    def mean(self):
+        return self.total / self.count if self.count > 0 else float('nan')
+
+    def __len__(self):
+        return self.count
+
+    def __repr__(self):
+        return 'PooledMetric(mean=%r, count=%d)' % (self.mean(), self.count)
+
+
+def log_metric_sum(metric_dict, stat_str, total, count):
+    """``log_metric`` for values that arrive already summed (the evaluation kernel's per-scene sums and frame counts)."""
+    if stat_str not in metric_dict:
+        metric_dict[stat_str] = PooledMetric()
+    metric_dict[stat_str].add(total, count)
+    return metric_dict
+
+
+def log_metric(metric_dict, stat_str, metric_np):
+    """Add the values ``metric_np`` to the metric ``stat_str`` (reference src/utils/scenario_gen.py:120-124; pooled as a sum and
+    a count instead of a growing list)."""
+    import numpy as np
+    v = np.asarray(metric_np, dtype=np.float64).reshape(-1)
+    return log_metric_sum(metric_dict, stat_str, float(v.sum()), v.size)
+
+
+def log_freq_stat(freq_dict_cnt, freq_dict_total, stat_str, cnt_add, tot_add):
+    """Add ``cnt_add`` occurrences out of ``tot_add`` trials to ``stat_str`` (reference src/utils/scenario_gen.py:126-132)."""
+    if stat_str not in freq_dict_cnt:
+        freq_dict_cnt[stat_str] = 0
+        freq_dict_total[stat_str] = 0
+    freq_dict_cnt[stat_str] += cnt_add
+    freq_dict_total[stat_str] += tot_add
+    return freq_dict_cnt, freq_dict_total
+
+
+def print_metrics(metrics, freq_metrics_cnt, freq_metrics_total, log=print):
+    """One ``name = value`` line per metric (pooled mean) and per frequency (count / total), in insertion order (reference
+    src/utils/scenario_gen.py:134-138)."""
+    for k, v in metrics.items():
+        log('%s = %f' % (k, v.mean()))
+    for k, v in freq_metrics_cnt.items():
+        log('%s = %f' % (k, float(v) / freq_metrics_total[k]))
