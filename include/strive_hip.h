@@ -483,6 +483,45 @@ int strive_planner_eval_metrics(const double* plan, const float* others, const i
                                 const float* lw_others, int32_t B, int32_t NR, int32_t T, int32_t scale, double dt,
                                 int32_t* out_i, double* out_d, int32_t* status, strive_stream_t stream);
 
+/* Adversarial-scenario evaluation (reference src/eval_adv_gen.py:339-513 compute_metrics and :116-168 compute_coll_feat) of
+ * B scenes in ONE launch, float64 on the fp32 inputs, one workgroup per scene.
+ *   fut (NA,T,4) every scene's fut_adv, the ego first; ptr (B+1) offsets into fut / lw / z; lw (NA,2); atk_agt (B) the JSON's
+ *   attack_agt; dt (B); z, mu, var (NA,D), D = 1..64, or all three NULL (no log-likelihood); plan_fit (B,T,4) the
+ *   fut_internal_ego rows read where has_fit (B) is set; map + mapix (B) + lin_tab, or a NULL map (no environment terms);
+ *   lin_tab holds the fp32 linspace(-1, 1, k) tables for k = 1..lin_max one after the other (table k starts at k(k-1)/2);
+ *   want_feat (B) asks for the collision features.
+ * Per scene: the ego against every other agent at the coarse steps (check_single_veh_coll, reference
+ * src/losses/adv_gen_nusc.py:517-565; hit = IoU > 0.02, NaN frames skipped) -> adv_collide, coll_t = amin of the first-hit
+ * times (T without a hit), coll_agt = argmin + 1; the effective attacker is coll_agt after a hit, else atk_agt, the "others"
+ * every agent but the ego and that attacker.  With coll_t > 0: check_pairwise_veh_coll (:567-623) on the non-ego agents over
+ * [0, coll_t) -- the reference's early breaks make its coll_count the number of agents i overlapping some j > i at some
+ * step -- and, with a map, compute_coll_rate_env_from_traj (src/losses/traffic_model.py:421-463) / check_on_layer
+ * (src/datasets/nuscenes_utils.py:266-298) with the grid L = round(mean_l / mean(dx)) from the scene's valid rows.  Then
+ * compute_accels (:323-337) over [0, coll_t) for the attacker (coll_t > 2) and the others, log_normal
+ * (src/losses/common.py:26-42) of the attacker's and the others' latents, the planner fit over [0, coll_t), and the
+ * collision features at the first x5 up-sampled contact (transform2frame, src/utils/transforms.py:78-139).
+ *   out_i (B,20) int32 : adv_collide, coll_t, coll_agt, atk_agt, num_coll_veh, num_traj_veh, env_coll_atk, env_coll_others,
+ *                        n_others, env_L, env_W, atk_accel_cnt, other_accel_cnt, ll_other_cnt, fit_cnt, feat_status (-1 not
+ *                        asked, 0 found, 1 no fine-step contact), fine_t, fine_agt, lr_coll_t, env_frames; -1 = absent
+ *   out_d (B,26) double: (sum, max) of |accel|, forward, lateral for the attacker, the same six for the others, ll_atk,
+ *                        ll_other_sum, fit_pos_sum, fit_ang_rad_sum, fit_ang_deg_sum, hvec (2), angvec (2), h, ang, rel_s,
+ *                        env_mean_l, env_mean_w; NaN = absent
+ *   status (B) int32   : 0 = written; 1 = ego only; 2 = offsets, attack_agt or map index out of range; 3 = more than 63
+ *                        others; 4 = the sampling grid exceeds lin_max (outputs untouched for every non-zero status)
+ * A scene's outputs are bit-identical whatever else is in the batch.  T >= 2. */
+int strive_scenario_eval_metrics(const float* fut, const int32_t* ptr, const float* lw, const int32_t* atk_agt, const double* dt,
+                                 const float* z, const float* mu, const float* var, int32_t D, const float* plan_fit,
+                                 const int32_t* has_fit, const StriveMap* map, const int32_t* mapix, const float* lin_tab,
+                                 int32_t lin_max, const int32_t* want_feat, int32_t B, int32_t NA, int32_t T, int32_t* out_i,
+                                 double* out_d, int32_t* status, strive_stream_t stream);
+
+/* One Lloyd step of k-means on x (N,F) float64 with centers (k,F), F = 1..8, k = 1..64 (the clustering of reference
+ * src/cluster_scenarios.py, which calls scikit-learn's KMeans on the host): labels (N) = nearest centre, the lowest index on
+ * equal squared distance; mind (N) that distance; sums (k,F) and counts (k) per cluster; inertia (1) = sum of mind.  Two
+ * launches; the sums are reduced in a fixed order without atomics on doubles, so two runs give the same bytes. */
+int strive_kmeans_step(const double* x, const double* centers, int32_t N, int32_t F, int32_t k, int32_t* labels, double* mind,
+                       double* sums, int32_t* counts, double* inertia, strive_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Training backward (weight gradients) -- reference src/train_traffic.py:103-131 calls loss.backward() through
  * TrafficModel.forward (src/models/traffic_model.py:178-225).

@@ -165,6 +165,8 @@ PROTOTYPES = {
     'strive_interp_traj_bwd': (C.c_int, [P, P, I, I, I, I, P, P, P, P, P, P]),
     'strive_rect_iou': (C.c_int, [P, P, P, P, I, P, P]),
     'strive_planner_eval_metrics': (C.c_int, [P, P, P, P, P, I, I, I, I, C.c_double, P, P, P, P]),
+    'strive_scenario_eval_metrics': (C.c_int, [P, P, P, P, P, P, P, P, I, P, P, C.POINTER(StriveMap), P, P, I, P, I, I, I, P, P, P, P]),
+    'strive_kmeans_step': (C.c_int, [P, P, I, I, I, P, P, P, P, P, P]),
     'strive_veh_coll_bwd': (C.c_int, [C.POINTER(StriveScenes), P, I, P, I, P, P, C.c_float, P, P, P, P]),
     'strive_avoid_coll_workspace_bytes': (SZ, [C.POINTER(StriveScenes), C.POINTER(StriveAvoidColl), I]),
     'strive_avoid_coll_fwd': (C.c_int, [C.POINTER(StriveScenes), C.POINTER(StriveMap), C.POINTER(StriveAvoidColl), P, I, P, P, P,

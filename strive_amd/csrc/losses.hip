@@ -584,6 +584,538 @@ extern "C" int strive_planner_eval_metrics(const double* plan, const float* othe
     return 0;
 }
 
+// =============================================================================================
+// Adversarial-scenario evaluation (reference src/eval_adv_gen.py:339-513 compute_metrics and :116-168 compute_coll_feat) for
+// B scenes in ONE launch, float64 on the fp32 inputs, one workgroup per scene; nothing is shared between scenes, every
+// cross-thread result is an integer minimum / flag or is added by one thread in index order, so a scene's outputs are
+// bit-identical whatever else is in the batch.  Per scene, in the reference's order:
+//   1. ego (agent 0) against every other agent at the coarse steps (check_single_veh_coll, src/losses/adv_gen_nusc.py:517-565:
+//      hit = IoU > 0.02, frames holding NaN skipped): the key step * (n-1) + agent enters a shared integer minimum, which IS
+//      (np.amin, np.argmin) of the first-hit times: CT (T without a hit) and coll_agt = argmin + 1.  The effective attacker
+//      is coll_agt after a hit, else the JSON's attack_agt; the "others" are every agent but the ego and that attacker.
+//   2. CT > 0: check_pairwise_veh_coll (:567-623) on the non-ego agents over steps [0, CT).  The reference leaves the j loop
+//      once agent i is marked and the t loop at the first hit, so its coll_count is incremented exactly once per marked agent:
+//      coll_count == number of agents i that overlap SOME j > i at SOME step.  That set does not depend on the order of
+//      evaluation: the workgroup strides over all (pair, step) and sets flags.  (A NaN pose gives a NaN IoU, which is no hit.)
+//   3. CT > 0 and a map: compute_coll_rate_env_from_traj (src/losses/traffic_model.py:421-463) -> check_on_layer
+//      (src/datasets/nuscenes_utils.py:266-298) on the frames [0, CT) of ALL agents that hold no NaN.  The sampling grid is
+//      L = round(mean_l / mean(dx)), W likewise, the mean of lw over the valid (agent, step) rows of the scene (the reference's
+//      expanded tensor), formed here in float64 from the per-agent frame counts; samples are (linspace(-1,1,L) * l) / 2 in
+//      fp32 from the caller's table, pixels by crop_dev.h (fp64 divide, round half even, out of bounds -> pixel (0,0)); a
+//      frame is off road when fp32(count) / fp32(L*W) < fp32(1 - 0.05).
+//   4. compute_accels (:323-337) over [0, CT): the attacker when CT > 2; the others' series concatenated in agent order.
+//   5. log_normal (src/losses/common.py:26-42) of the attacker's latent row and of the others' rows.
+//   6. planner fit over [0, CT): position error, angle between the unit headings (dot product clamped to [-1, 1]).
+//   7. want_feat: compute_coll_feat -- ego and others up-sampled x5 in fp32 (interp_traj, headings renormalised), first hit
+//      per agent at the fine steps as in 1., the attacker's pose in the ego's frame at that fine step (transform2frame,
+//      src/utils/transforms.py:78-139), rel_s from the coarse frames at lr_coll_t = int((t_fine * (dt / 5)) / dt).
+//   out_i (B, 20): adv_collide, coll_t, coll_agt, atk_agt (effective), num_coll_veh, num_traj_veh, env_coll_atk, env_coll_others,
+//                  n_others, env_L, env_W, atk_accel_cnt, other_accel_cnt, ll_other_cnt, fit_cnt, feat_status (-1 not asked,
+//                  0 found, 1 no fine-step contact), fine_t, fine_agt (row among the others), lr_coll_t, env_frames; -1 = absent
+//   out_d (B, 26): attacker (sum, max) of |accel|, forward, lateral; the same six for the others; ll_atk, ll_other_sum,
+//                  fit_pos_sum, fit_ang_rad_sum, fit_ang_deg_sum, hvec (2), angvec (2), h, ang, rel_s, env_mean_l, env_mean_w;
+//                  NaN = absent
+//   status (B)   : 0 written; 1 ego only; 2 offsets / attack_agt / map index out of range; 3 more than 63 others; 4 the
+//                  sampling grid exceeds the caller's linspace table (outputs untouched for every non-zero status)
+// =============================================================================================
+#include "crop_dev.h"
+
+#define SE_NI 20
+#define SE_ND 26
+#define SE_MAX_OTHERS 63
+#define SE_MAX_PAIRS (SE_MAX_OTHERS * (SE_MAX_OTHERS - 1) / 2)
+#define SE_FEAT_SCALE 5
+#define SE_LOG_SQRT_2PI 0.91893853320467274178      // math.log(math.sqrt(2 * math.pi))
+
+struct ScenarioEvalArgs {
+    const float* fut; const int32_t* ptr; const float* lw; const int32_t* atk_agt; const double* dt;
+    const float* z; const float* mu; const float* var; int D;
+    const float* plan_fit; const int32_t* has_fit;
+    int has_map; const int32_t* mapix; const float* lin_tab; int lin_max;
+    const int32_t* want_feat;
+    int NA, T;
+    int32_t* out_i; double* out_d; int32_t* status;
+};
+
+__device__ __forceinline__ bool se_nan4(const float* p) { return p[0] != p[0] || p[1] != p[1] || p[2] != p[2] || p[3] != p[3]; }
+
+// IoU of two fp32 poses (NaN in, NaN out of the comparison: callers test se_nan4 first where the reference skips)
+__device__ __forceinline__ double se_iou(const float* a, const float* lwa, const float* b, const float* lwb) {
+    double ax[4], ay[4], bx[4], by[4];
+    box_corners(a, lwa, ax, ay);
+    box_corners(b, lwb, bx, by);
+    return quad_clip_iou(ax, ay, bx, by);
+}
+
+// one fine frame of interp_traj in fp32 (the taps of planner_eval_kernel), heading renormalised
+__device__ __forceinline__ void se_fine_frame(const float* tr, int T, int j, float rs_f, float u[4]) {
+    float src = __fsub_rn(__fmul_rn(rs_f, __fadd_rn((float)j, 0.5f)), 0.5f);
+    src = src < 0.f ? 0.f : src;
+    int i0 = (int)src;
+    i0 = i0 > T - 1 ? T - 1 : i0;
+    const int i1 = i0 < T - 1 ? i0 + 1 : i0;
+    const float w1 = __fsub_rn(src, (float)i0), w0 = __fsub_rn(1.0f, w1);
+    for (int c = 0; c < 4; ++c) u[c] = __fadd_rn(__fmul_rn(w0, tr[i0 * 4 + c]), __fmul_rn(w1, tr[i1 * 4 + c]));
+    const float nrm = sqrtf(__fadd_rn(__fmul_rn(u[2], u[2]), __fmul_rn(u[3], u[3])));
+    u[2] = u[2] / nrm;
+    u[3] = u[3] / nrm;
+}
+
+// compute_accels (reference src/eval_adv_gen.py:323-337) on the first m frames of one fp32 trajectory, frame 0 upwards
+__device__ __forceinline__ void se_accels(const float* tr, int m, double dt, double sum[3], double mx[3], int& cnt) {
+#pragma clang fp contract(off)                       // every operation rounded on its own: the same bits on the device and on a host
+    double s_prev = 0.0, vx_prev = 0.0, vy_prev = 0.0, lx_prev = 0.0, ly_prev = 0.0;
+    for (int i = 0; i + 1 < m; ++i) {
+        const double dx = ((double)tr[(i + 1) * 4 + 0] - (double)tr[i * 4 + 0]) / dt;
+        const double dy = ((double)tr[(i + 1) * 4 + 1] - (double)tr[i * 4 + 1]) / dt;
+        const double s = sqrt(dx * dx + dy * dy);
+        const double hx = (double)tr[i * 4 + 2], hy = (double)tr[i * 4 + 3];
+        const double hn = sqrt(hx * hx + hy * hy);
+        const double ux = hx / hn, uy = hy / hn;
+        const double vx = s * ux, vy = s * uy;
+        if (i > 0) {
+            const double fwd = fabs((s - s_prev) / dt);
+            const double acx = (vx - vx_prev) / dt, acy = (vy - vy_prev) / dt;
+            const double lat = fabs(acx * lx_prev + acy * ly_prev);
+            const double acc = sqrt(acx * acx + acy * acy);
+            const double v[3] = {acc, fwd, lat};
+            for (int c = 0; c < 3; ++c) {
+                sum[c] += v[c];
+                mx[c] = (cnt == 0 || v[c] > mx[c] || v[c] != v[c]) ? v[c] : mx[c];
+            }
+            ++cnt;
+        }
+        s_prev = s; vx_prev = vx; vy_prev = vy;
+        lx_prev = -uy; ly_prev = ux;
+    }
+}
+
+__global__ __launch_bounds__(256) void scenario_eval_kernel(ScenarioEvalArgs A, StriveMap map) {
+#pragma clang fp contract(off)
+    __shared__ int s_key, s_fkey, s_L, s_W, s_env_ok;
+    __shared__ int s_mark[SE_MAX_OTHERS + 1], s_env[SE_MAX_OTHERS + 1], s_cnt[SE_MAX_OTHERS + 1], s_acnt[SE_MAX_OTHERS + 1];
+    __shared__ double s_ll[SE_MAX_OTHERS + 1], s_asum[SE_MAX_OTHERS + 1][3], s_amax[SE_MAX_OTHERS + 1][3];
+    __shared__ unsigned char s_pi[SE_MAX_PAIRS], s_pj[SE_MAX_PAIRS];
+    const double kNaN = __longlong_as_double(0x7ff8000000000000ll);
+    const int b = blockIdx.x, tid = threadIdx.x, T = A.T;
+    const int a0 = A.ptr[b], n = A.ptr[b + 1] - a0, nO = n - 1;
+    int st = 0;
+    if (n <= 0 || a0 < 0 || a0 + n > A.NA) st = 2;
+    else if (n == 1) st = 1;
+    else if (nO > SE_MAX_OTHERS) st = 3;
+    else if (A.atk_agt[b] < 0 || A.atk_agt[b] >= n) st = 2;
+    else if (A.has_map && (A.mapix[b] < 0 || A.mapix[b] >= map.M)) st = 2;
+    if (st != 0) {
+        if (tid == 0) A.status[b] = st;
+        return;
+    }
+    const float* fut = A.fut + (size_t)a0 * T * 4;         // (n, T, 4), the ego first
+    const float* lw = A.lw + (size_t)a0 * 2;
+    const double dt = A.dt[b];
+    if (tid == 0) {
+        s_key = 0x7fffffff;
+        s_fkey = 0x7fffffff;
+        s_env_ok = 1;
+    }
+    if (tid <= SE_MAX_OTHERS) {
+        s_mark[tid] = 0;
+        s_env[tid] = 0;
+    }
+    __syncthreads();
+
+    // ---- 1. ego against the others, coarse steps ----
+    for (int e = tid; e < nO * T; e += 256) {
+        const int t = e / nO, al = e - t * nO;               // e IS the key step * nO + agent
+        const float* pe = fut + (size_t)t * 4;
+        const float* po = fut + ((size_t)(al + 1) * T + t) * 4;
+        if (se_nan4(pe) || se_nan4(po)) continue;
+        if (se_iou(pe, lw, po, lw + (al + 1) * 2) > PLAN_EVAL_IOU_THRESH) {
+            atomicMin(&s_key, e);                            // this thread's keys only grow from here
+            break;
+        }
+    }
+    __syncthreads();
+    const int key = s_key;
+    const bool did = key != 0x7fffffff;
+    const int CT = did ? key / nO : T;
+    const int coll_agt = did ? key - CT * nO + 1 : 1;        // np.argmin of an all-T array is 0
+    const int atk = did ? coll_agt : A.atk_agt[b];
+    const int n_others = nO - (atk != 0 ? 1 : 0);
+
+    // ---- 2. pairs of non-ego agents before the crash ----
+    const int npairs = nO * (nO - 1) / 2;
+    if (CT > 0 && npairs > 0) {
+        if (tid < nO) {
+            int off = tid * (2 * nO - tid - 1) / 2;
+            for (int j = tid + 1; j < nO; ++j, ++off) {
+                s_pi[off] = (unsigned char)tid;
+                s_pj[off] = (unsigned char)j;
+            }
+        }
+        __syncthreads();
+        for (int e = tid; e < npairs * CT; e += 256) {
+            const int p = e / CT, t = e - p * CT;
+            const int i = s_pi[p], j = s_pj[p];
+            const float* pa = fut + ((size_t)(i + 1) * T + t) * 4;
+            const float* pb = fut + ((size_t)(j + 1) * T + t) * 4;
+            if (se_iou(pa, lw + (i + 1) * 2, pb, lw + (j + 1) * 2) > PLAN_EVAL_IOU_THRESH) atomicOr(&s_mark[i], 1);
+        }
+    }
+
+    // ---- 3. drivable fraction of every valid frame before the crash ----
+    const bool do_env = CT > 0 && A.has_map;
+    if (do_env) {
+        if (tid < n) {
+            int c = 0;
+            for (int t = 0; t < CT; ++t) c += se_nan4(fut + ((size_t)tid * T + t) * 4) ? 0 : 1;
+            s_cnt[tid] = c;
+        }
+        __syncthreads();
+        if (tid == 0) {
+            long long tot = 0;
+            double sl = 0.0, sw = 0.0, sdx = 0.0;
+            for (int a = 0; a < n; ++a) {
+                tot += s_cnt[a];
+                sl += (double)s_cnt[a] * (double)lw[a * 2 + 0];
+                sw += (double)s_cnt[a] * (double)lw[a * 2 + 1];
+            }
+            for (int m = 0; m < map.M * 2; ++m) sdx += map.dx[m];
+            const double mdx = sdx / (double)(map.M * 2);
+            int L = 0, W = 0;
+            double ml = kNaN, mw = kNaN;
+            if (tot > 0) {
+                ml = sl / (double)tot;
+                mw = sw / (double)tot;
+                const double ql = rint(ml / mdx), qw = rint(mw / mdx);
+                L = (ql >= 1.0 && ql <= (double)A.lin_max) ? (int)ql : -1;
+                W = (qw >= 1.0 && qw <= (double)A.lin_max) ? (int)qw : -1;
+                if (L < 0 || W < 0) s_env_ok = 0;
+            }
+            s_L = L;
+            s_W = W;
+            s_ll[0] = ml;                                    // (scratch: s_ll is filled in step 5)
+            s_ll[1] = mw;
+        }
+        __syncthreads();
+        if (!s_env_ok) {
+            if (tid == 0) A.status[b] = 4;
+            return;
+        }
+    }
+    double env_ml = kNaN, env_mw = kNaN;
+    int env_frames = -1;
+    if (do_env) {
+        const int L = s_L, W = s_W;
+        env_ml = s_ll[0];
+        env_mw = s_ll[1];
+        const int m = A.mapix[b];
+        const float* lin_l = A.lin_tab + (size_t)L * (L - 1) / 2;     // linspace(-1, 1, k) starts at k (k - 1) / 2
+        const float* lin_w = A.lin_tab + (size_t)W * (W - 1) / 2;
+        const float thresh = (float)(1.0 - 0.05), area = (float)(L * W);
+        for (int e = tid; L > 0 && e < n * CT; e += 256) {
+            const int a = e / CT, t = e - a * CT;
+            const float* p = fut + ((size_t)a * T + t) * 4;
+            if (se_nan4(p)) continue;
+            CropFrame fr;
+            fr.x = p[0]; fr.y = p[1]; fr.hc = p[2]; fr.hs = p[3];
+            set_crop_scale(fr, map.dx[m * 2 + 0], map.dx[m * 2 + 1]);
+            fr.H = map.H;
+            fr.W = map.W;
+            fr.base = map.raster + (size_t)m * map.C * map.H * map.W;      // layer 0
+            const float ls = lw[a * 2 + 0], ws = lw[a * 2 + 1];
+            int on = 0;
+            for (int i = 0; i < L; ++i) {
+                const float lwise = __fmul_rn(lin_l[i], ls) * 0.5f;
+                for (int j = 0; j < W; ++j) {
+                    const float wwise = __fmul_rn(lin_w[j], ws) * 0.5f;
+                    int px, py;
+                    float gx, gy;
+                    crop_world(fr, lwise, wwise, gx, gy);
+                    world_to_pixel(fr, gx, gy, px, py);
+                    on += fr.base[(size_t)py * map.W + px] != 0 ? 1 : 0;
+                }
+            }
+            if (__fdiv_rn((float)on, area) < thresh) atomicOr(&s_env[a], 1);
+        }
+        if (tid == 0) {
+            env_frames = 0;
+            for (int a = 0; a < n; ++a) env_frames += s_cnt[a];
+        }
+    }
+    __syncthreads();                                          // s_ll scratch read, s_mark / s_env complete
+
+    // ---- 4. accelerations and 5. latent log-likelihood, one agent per thread ----
+    if (tid < n) {
+        double sum[3] = {0.0, 0.0, 0.0}, mx[3] = {0.0, 0.0, 0.0};
+        int cnt = 0;
+        if (CT > 2) se_accels(fut + (size_t)tid * T * 4, CT, dt, sum, mx, cnt);
+        s_acnt[tid] = cnt;
+        for (int c = 0; c < 3; ++c) {
+            s_asum[tid][c] = sum[c];
+            s_amax[tid][c] = mx[c];
+        }
+        double ll = kNaN;
+        if (A.z) {
+            ll = 0.0;
+            const size_t r = (size_t)(a0 + tid) * A.D;
+            for (int d = 0; d < A.D; ++d) {
+                const double x = (double)A.z[r + d], m = (double)A.mu[r + d], v = (double)A.var[r + d];
+                ll += -log(sqrt(v)) - SE_LOG_SQRT_2PI - ((x - m) * (x - m)) / (2.0 * v);
+            }
+        }
+        s_ll[tid] = ll;
+    }
+
+    // ---- 7. (first part) fine-step contact ----
+    const bool feat = A.want_feat[b] != 0;
+    const int TO = T * SE_FEAT_SCALE;
+    const float rs_f = (float)(1.0 / (double)SE_FEAT_SCALE);
+    if (feat) {
+        for (int e = tid; e < nO * TO; e += 256) {
+            const int j = e / nO, al = e - j * nO;
+            float g[4], u[4];
+            se_fine_frame(fut + (size_t)(al + 1) * T * 4, T, j, rs_f, u);
+            if (se_nan4(u)) continue;
+            se_fine_frame(fut, T, j, rs_f, g);
+            if (se_nan4(g)) continue;
+            if (se_iou(g, lw, u, lw + (al + 1) * 2) > PLAN_EVAL_IOU_THRESH) {
+                atomicMin(&s_fkey, e);
+                break;
+            }
+        }
+    }
+    __syncthreads();
+    if (tid != 0) return;
+
+    int32_t* oi = A.out_i + (size_t)b * SE_NI;
+    double* od = A.out_d + (size_t)b * SE_ND;
+    for (int c = 0; c < SE_NI; ++c) oi[c] = -1;
+    for (int c = 0; c < SE_ND; ++c) od[c] = kNaN;
+    oi[0] = did ? 1 : 0;
+    oi[1] = CT;
+    oi[2] = coll_agt;
+    oi[3] = atk;
+    oi[8] = n_others;
+    if (CT > 0) {
+        int marked = 0;
+        for (int i = 0; i < nO; ++i) marked += s_mark[i];
+        oi[4] = marked;
+        oi[5] = nO;
+    }
+    if (do_env) {
+        int oth = 0;
+        for (int a = 1; a < n; ++a) oth += (a != atk) ? s_env[a] : 0;
+        oi[6] = s_env[atk];
+        oi[7] = oth;
+        oi[9] = s_L;
+        oi[10] = s_W;
+        oi[19] = env_frames;
+        od[24] = env_ml;
+        od[25] = env_mw;
+    }
+    // accelerations: the attacker's block, then the others' series in agent order
+    oi[11] = s_acnt[atk];
+    if (s_acnt[atk] > 0)
+        for (int c = 0; c < 3; ++c) {
+            od[2 * c] = s_asum[atk][c];
+            od[2 * c + 1] = s_amax[atk][c];
+        }
+    {
+        int cnt = 0;
+        double sum[3] = {0.0, 0.0, 0.0}, mx[3] = {0.0, 0.0, 0.0};
+        for (int a = 1; a < n; ++a) {
+            if (a == atk || s_acnt[a] == 0) continue;
+            for (int c = 0; c < 3; ++c) {
+                sum[c] += s_asum[a][c];
+                const double v = s_amax[a][c];
+                mx[c] = (cnt == 0 || v > mx[c] || v != v) ? v : mx[c];
+            }
+            cnt += s_acnt[a];
+        }
+        oi[12] = cnt;
+        if (cnt > 0)
+            for (int c = 0; c < 3; ++c) {
+                od[6 + 2 * c] = sum[c];
+                od[7 + 2 * c] = mx[c];
+            }
+    }
+    if (A.z) {
+        od[12] = s_ll[atk];
+        double sum = 0.0;
+        for (int a = 1; a < n; ++a) sum += (a != atk) ? s_ll[a] : 0.0;
+        oi[13] = n_others;
+        if (n_others > 0) od[13] = sum;
+    }
+    if (A.has_fit[b]) {
+        const float* pf = A.plan_fit + (size_t)b * T * 4;
+        double sp = 0.0, sr = 0.0, sd = 0.0;
+        for (int t = 0; t < CT; ++t) {
+            const double ex = (double)fut[t * 4 + 0] - (double)pf[t * 4 + 0], ey = (double)fut[t * 4 + 1] - (double)pf[t * 4 + 1];
+            sp += sqrt(ex * ex + ey * ey);
+            const double gx = (double)fut[t * 4 + 2], gy = (double)fut[t * 4 + 3], qx = (double)pf[t * 4 + 2], qy = (double)pf[t * 4 + 3];
+            const double gn = sqrt(gx * gx + gy * gy), qn = sqrt(qx * qx + qy * qy);
+            double dot = (gx / gn) * (qx / qn) + (gy / gn) * (qy / qn);
+            dot = dot < -1.0 ? -1.0 : (dot > 1.0 ? 1.0 : dot);
+            const double ang = acos(dot);
+            sr += ang;
+            sd += ang * (180.0 / 3.14159265358979323846);
+        }
+        oi[14] = CT;
+        od[14] = sp;
+        od[15] = sr;
+        od[16] = sd;
+    }
+    if (feat) {
+        const int fkey = s_fkey;
+        if (fkey == 0x7fffffff) {
+            oi[15] = 1;
+        } else {
+            const int ft = fkey / nO, fa = fkey - ft * nO;
+            float g[4], u[4];
+            se_fine_frame(fut, T, ft, rs_f, g);
+            se_fine_frame(fut + (size_t)(fa + 1) * T * 4, T, ft, rs_f, u);
+            // transform2frame(ego, attacker): heading Rp Rf, position Rf (p - f)
+            const double fc = (double)g[2], fs = (double)g[3], pc = (double)u[2], ps = (double)u[3];
+            const double hc = pc * fc + ps * fs, hs = ps * fc - pc * fs;
+            const double ddx = (double)u[0] - (double)g[0], ddy = (double)u[1] - (double)g[1];
+            const double lx = fc * ddx + fs * ddy, ly = -fs * ddx + fc * ddy;
+            const double ln = sqrt(lx * lx + ly * ly);
+            const double interp_dt = dt / (double)SE_FEAT_SCALE;
+            const int lr = (int)(__dmul_rn((double)ft, interp_dt) / dt);          // (sic) the reference's order of operations
+            const int f1 = lr > 0 ? lr : lr + 1, f0 = f1 - 1;
+            const float* q = fut + (size_t)(fa + 1) * T * 4;
+            const double rx = ((double)fut[f1 * 4 + 0] - (double)fut[f0 * 4 + 0]) / dt - ((double)q[f1 * 4 + 0] - (double)q[f0 * 4 + 0]) / dt;
+            const double ry = ((double)fut[f1 * 4 + 1] - (double)fut[f0 * 4 + 1]) / dt - ((double)q[f1 * 4 + 1] - (double)q[f0 * 4 + 1]) / dt;
+            oi[15] = 0;
+            oi[16] = ft;
+            oi[17] = fa;
+            oi[18] = lr;
+            od[17] = hc;
+            od[18] = hs;
+            od[19] = lx / ln;
+            od[20] = ly / ln;
+            od[21] = atan2(hs, hc);
+            od[22] = atan2(ly / ln, lx / ln);
+            od[23] = sqrt(rx * rx + ry * ry);
+        }
+    }
+    A.status[b] = 0;
+}
+
+extern "C" int strive_scenario_eval_metrics(const float* fut, const int32_t* ptr, const float* lw, const int32_t* atk_agt,
+                                            const double* dt, const float* z, const float* mu, const float* var, int32_t D,
+                                            const float* plan_fit, const int32_t* has_fit, const StriveMap* map,
+                                            const int32_t* mapix, const float* lin_tab, int32_t lin_max, const int32_t* want_feat,
+                                            int32_t B, int32_t NA, int32_t T, int32_t* out_i, double* out_d, int32_t* status,
+                                            strive_stream_t stream) {
+    STRIVE_CHECK_ARG(fut && ptr && lw && atk_agt && dt && plan_fit && has_fit && want_feat && out_i && out_d && status, "null argument");
+    STRIVE_CHECK_ARG((z && mu && var) || (!z && !mu && !var), "z, mu and var must be given together");
+    STRIVE_CHECK_ARG(!z || (D >= 1 && D <= 64), "latent size must be 1..64");
+    STRIVE_CHECK_ARG(!map || (mapix && lin_tab && lin_max >= 1), "a map needs mapix and the linspace table");
+    STRIVE_CHECK_ARG(!map || (map->raster && map->dx && map->M >= 1 && map->C >= 1 && map->H >= 1 && map->W >= 1), "bad map");
+    STRIVE_CHECK_ARG(T >= 2 && T <= 4096, "T must be 2..4096");
+    STRIVE_CHECK_ARG(NA >= 0, "bad NA");
+    if (B <= 0) return 0;
+    ScenarioEvalArgs A;
+    A.fut = fut; A.ptr = ptr; A.lw = lw; A.atk_agt = atk_agt; A.dt = dt;
+    A.z = z; A.mu = mu; A.var = var; A.D = D;
+    A.plan_fit = plan_fit; A.has_fit = has_fit;
+    A.has_map = map ? 1 : 0; A.mapix = mapix; A.lin_tab = lin_tab; A.lin_max = lin_max;
+    A.want_feat = want_feat;
+    A.NA = NA; A.T = T;
+    A.out_i = out_i; A.out_d = out_d; A.status = status;
+    StriveMap m;
+    memset(&m, 0, sizeof(m));
+    if (map) m = *map;
+    hipLaunchKernelGGL(scenario_eval_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, A, m);
+    STRIVE_CHECK_LAUNCH();
+    return 0;
+}
+
+// =============================================================================================
+// One Lloyd step of k-means on N x F float64 features (the clustering of reference src/cluster_scenarios.py, whose
+// KMeans.fit / .predict run scikit-learn on the host): every row's nearest centre (squared distance summed over the
+// features in order, the lowest index on equal distance), then per-cluster sums and counts and the inertia.  No atomics on
+// doubles: workgroup j of the second launch owns cluster j (workgroup k the inertia), every thread adds its rows in
+// ascending order and the 256 partials meet in a fixed binary tree, so two runs give the same bytes.
+// =============================================================================================
+#define KM_MAX_F 8
+#define KM_MAX_K 64
+
+__global__ __launch_bounds__(256) void kmeans_assign_kernel(const double* __restrict__ x, const double* __restrict__ cen, int N, int F,
+                                                              int k, int32_t* __restrict__ labels, double* __restrict__ mind) {
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= N) return;
+    double v[KM_MAX_F];
+    for (int f = 0; f < F; ++f) v[f] = x[(size_t)r * F + f];
+    double best = 0.0;
+    int bj = 0;
+    for (int j = 0; j < k; ++j) {
+        double d = 0.0;
+        for (int f = 0; f < F; ++f) {
+            const double e = v[f] - cen[j * F + f];
+            d += e * e;
+        }
+        if (j == 0 || d < best) {
+            best = d;
+            bj = j;
+        }
+    }
+    labels[r] = bj;
+    mind[r] = best;
+}
+
+__global__ __launch_bounds__(256) void kmeans_reduce_kernel(const double* __restrict__ x, const int32_t* __restrict__ labels,
+                                                              const double* __restrict__ mind, int N, int F, int k,
+                                                              double* __restrict__ sums, int32_t* __restrict__ counts,
+                                                              double* __restrict__ inertia) {
+    __shared__ double s_acc[256][KM_MAX_F + 1];
+    __shared__ int s_n[256];
+    const int j = blockIdx.x, tid = threadIdx.x;
+    double acc[KM_MAX_F] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    int cnt = 0;
+    if (j < k) {
+        for (int r = tid; r < N; r += 256)
+            if (labels[r] == j) {
+                for (int f = 0; f < F; ++f) acc[f] += x[(size_t)r * F + f];
+                ++cnt;
+            }
+    } else {
+        for (int r = tid; r < N; r += 256) acc[0] += mind[r];
+    }
+    for (int f = 0; f < KM_MAX_F; ++f) s_acc[tid][f] = acc[f];
+    s_n[tid] = cnt;
+    __syncthreads();
+    for (int s = 128; s >= 1; s >>= 1) {
+        if (tid < s) {
+            for (int f = 0; f < KM_MAX_F; ++f) s_acc[tid][f] += s_acc[tid + s][f];
+            s_n[tid] += s_n[tid + s];
+        }
+        __syncthreads();
+    }
+    if (tid != 0) return;
+    if (j < k) {
+        for (int f = 0; f < F; ++f) sums[j * F + f] = s_acc[0][f];
+        counts[j] = s_n[0];
+    } else {
+        inertia[0] = s_acc[0][0];
+    }
+}
+
+extern "C" int strive_kmeans_step(const double* x, const double* centers, int32_t N, int32_t F, int32_t k, int32_t* labels,
+                                  double* mind, double* sums, int32_t* counts, double* inertia, strive_stream_t stream) {
+    STRIVE_CHECK_ARG(x && centers && labels && mind && sums && counts && inertia, "null argument");
+    STRIVE_CHECK_ARG(F >= 1 && F <= KM_MAX_F, "F must be 1..8");
+    STRIVE_CHECK_ARG(k >= 1 && k <= KM_MAX_K, "k must be 1..64");
+    STRIVE_CHECK_ARG(N >= 1, "N must be at least 1");
+    hipLaunchKernelGGL(kmeans_assign_kernel, dim3((N + 255) / 256), dim3(256), 0, (hipStream_t)stream, x, centers, N, F, k, labels, mind);
+    STRIVE_CHECK_LAUNCH();
+    hipLaunchKernelGGL(kmeans_reduce_kernel, dim3(k + 1), dim3(256), 0, (hipStream_t)stream, x, (const int32_t*)labels,
+                       (const double*)mind, N, F, k, sums, counts, inertia);
+    STRIVE_CHECK_LAUNCH();
+    return 0;
+}
+
 
 // =============================================================================================
 // AvoidCollLoss in one call per direction (reference src/losses/adv_gen_nusc.py:264-341).

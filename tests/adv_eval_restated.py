@@ -1,0 +1,286 @@
+"""float64 numpy restatement of strive_scenario_eval_metrics and strive_kmeans_step (strive_amd/csrc/losses.hip), formula by formula
+(reference src/eval_adv_gen.py:116-168, 323-513; src/losses/adv_gen_nusc.py:517-644; src/losses/traffic_model.py:421-463;
+src/datasets/nuscenes_utils.py:205-298, 416-428; src/losses/common.py:26-42; src/utils/transforms.py:78-139).  Test infrastructure only;
+nothing here is loaded by the product."""
+import numpy as np
+
+IOU_THRESH = 0.02
+FEAT_SCALE = 5
+LOG_SQRT_2PI = 0.91893853320467274178
+f32 = np.float32
+
+
+def corners(pose, lw):
+    hl, hw = 0.5 * float(lw[0]), 0.5 * float(lw[1])
+    h = np.arctan2(float(pose[3]), float(pose[2]))
+    c, s = np.cos(h), np.sin(h)
+    return [(lx * c - ly * s + float(pose[0]), lx * s + ly * c + float(pose[1])) for lx, ly in ((-hl, -hw), (hl, -hw), (hl, hw), (-hl, hw))]
+
+
+def area(p):
+    return 0.5 * abs(sum(p[i][0] * p[(i + 1) % len(p)][1] - p[(i + 1) % len(p)][0] * p[i][1] for i in range(len(p))))
+
+
+def quad_iou(a, b):
+    poly = list(a)
+    for e in range(4):
+        if not poly:
+            break
+        ex, ey = b[e]
+        dx, dy = b[(e + 1) % 4][0] - ex, b[(e + 1) % 4][1] - ey
+        out = []
+        for i in range(len(poly)):
+            p, q = poly[i], poly[(i + 1) % len(poly)]
+            si = dx * (p[1] - ey) - dy * (p[0] - ex)
+            sj = dx * (q[1] - ey) - dy * (q[0] - ex)
+            if si >= 0:
+                out.append(p)
+            if (si >= 0) != (sj >= 0):
+                t = si / (si - sj)
+                out.append((p[0] + t * (q[0] - p[0]), p[1] + t * (q[1] - p[1])))
+        poly = out
+    inter = area(poly) if len(poly) >= 3 else 0.0
+    return inter / (area(a) + area(b) - inter)
+
+
+def pose_iou(pa, lwa, pb, lwb):
+    """NaN where either pose holds a NaN."""
+    if np.isnan(pa).any() or np.isnan(pb).any():
+        return np.nan
+    return quad_iou(corners(pa, lwa), corners(pb, lwb))
+
+
+def interp32(x, scale):
+    """F.interpolate(mode='linear', align_corners=False) along axis -2 in fp32 + heading renormalisation, every operation rounded."""
+    x = np.asarray(x, dtype=f32)
+    T = x.shape[-2]
+    j = np.arange(T * scale).astype(f32)
+    src = np.maximum(f32(1.0 / scale) * (j + f32(0.5)) - f32(0.5), f32(0.0)).astype(f32)
+    i0 = np.minimum(np.floor(src).astype(np.int64), T - 1)
+    i1 = np.minimum(i0 + 1, T - 1)
+    w1 = (src - i0.astype(f32)).astype(f32)
+    w0 = (f32(1.0) - w1).astype(f32)
+    with np.errstate(invalid='ignore'):
+        u = ((w0[:, None] * x[..., i0, :]).astype(f32) + (w1[:, None] * x[..., i1, :]).astype(f32)).astype(f32)
+        nrm = np.sqrt(((u[..., 2] * u[..., 2]).astype(f32) + (u[..., 3] * u[..., 3]).astype(f32)).astype(f32)).astype(f32)
+        u[..., 2] = (u[..., 2] / nrm).astype(f32)
+        u[..., 3] = (u[..., 3] / nrm).astype(f32)
+    return u
+
+
+def accels(tr, m, dt):
+    """compute_accels on the first m frames of one (T,4) trajectory in float64 -> three series (m-2)."""
+    tr = np.asarray(tr, dtype=np.float64)[:m]
+    with np.errstate(invalid='ignore'):
+        v = (tr[1:, :2] - tr[:-1, :2]) / dt
+        s = np.sqrt(v[:, 0] * v[:, 0] + v[:, 1] * v[:, 1])
+        uh = tr[:, 2:4] / np.sqrt(tr[:, 2:3] * tr[:, 2:3] + tr[:, 3:4] * tr[:, 3:4])
+        pv = s[:, None] * uh[:-1]
+        fwd = np.abs((s[1:] - s[:-1]) / dt)
+        acc = (pv[1:] - pv[:-1]) / dt
+        lat = np.abs(acc[:, 0] * -uh[:-2, 1] + acc[:, 1] * uh[:-2, 0])
+        accn = np.sqrt(acc[:, 0] * acc[:, 0] + acc[:, 1] * acc[:, 1])
+    return accn, fwd, lat
+
+
+def seq_sum(series):
+    tot = 0.0
+    for x in series:
+        tot += float(x)
+    return tot
+
+
+def nan_max(series):
+    """the kernel's running maximum: a NaN replaces it, later larger values replace a number only"""
+    mx = None
+    for x in series:
+        x = float(x)
+        if mx is None or x > mx or x != x:
+            mx = x
+    return mx
+
+
+def drivable_count(raster0, dx, pose, lw, L, W):
+    """Number of the L x W samples of one car box on pixels marked 1 (check_on_layer: fp32 sample coordinates, fp64 divide, round
+    half to even, out of bounds -> pixel (0,0))."""
+    H, Wd = raster0.shape
+    import torch
+    lin_l, lin_w = torch.linspace(-1.0, 1.0, L).numpy(), torch.linspace(-1.0, 1.0, W).numpy()
+    x, y, hc, hs = [f32(v) for v in pose]
+    lwise = ((lin_l * f32(lw[0])).astype(f32) * f32(0.5)).astype(f32)[:, None]
+    wwise = ((lin_w * f32(lw[1])).astype(f32) * f32(0.5)).astype(f32)[None, :]
+    gx = (((lwise * hc).astype(f32) - (wwise * hs).astype(f32)).astype(f32) + x).astype(f32)
+    gy = (((lwise * hs).astype(f32) + (wwise * hc).astype(f32)).astype(f32) + y).astype(f32)
+    px = np.rint(gx.astype(np.float64) / float(dx[0]))
+    py = np.rint(gy.astype(np.float64) / float(dx[1]))
+    inside = (px >= 0) & (px < Wd) & (py >= 0) & (py < H)
+    px = np.where(inside, px, 0).astype(np.int64)
+    py = np.where(inside, py, 0).astype(np.int64)
+    return int((raster0[py, px] != 0).sum())
+
+
+def scene_metrics(fut, lw, atk_agt, dt, z=None, mu=None, var=None, fit=None, raster=None, dx=None, mapix=0, want_feat=False):
+    """One scene -> dict with the kernel's integer columns (``i``), float columns (``d``), for every summed float column the sum of
+    the absolute values of its terms (``abs``), and the tie margins (``margin_iou``, ``margin_frac`` in samples, ``margin_grid``)."""
+    fut = np.asarray(fut, dtype=f32)
+    lw = np.asarray(lw, dtype=f32)
+    n, T = fut.shape[0], fut.shape[1]
+    nO = n - 1
+    nan = float('nan')
+    I, Dd, A = {}, {}, {}
+    margin = np.inf
+    times = np.full((nO,), T, dtype=np.int64)
+    for al in range(nO):
+        for t in range(T):
+            iou = pose_iou(fut[0, t], lw[0], fut[al + 1, t], lw[al + 1])
+            if np.isnan(iou):
+                continue
+            margin = min(margin, abs(iou - IOU_THRESH))
+            if iou > IOU_THRESH:
+                times[al] = t
+                break
+    did = bool((times < T).any())
+    CT, coll_agt = int(times.min()), int(times.argmin()) + 1
+    atk = coll_agt if did else int(atk_agt)
+    others = [a for a in range(1, n) if a != atk]
+    I.update(adv_collide=int(did), coll_t=CT, coll_agt=coll_agt, atk_agt=atk, n_others=len(others))
+    I.update(num_coll_veh=-1, num_traj_veh=-1, env_coll_atk=-1, env_coll_others=-1, env_L=-1, env_W=-1, env_frames=-1)
+    Dd.update(env_mean_l=nan, env_mean_w=nan)
+    margin_frac, margin_grid = np.inf, np.inf
+    if CT > 0:
+        marks = np.zeros((nO,), dtype=np.int64)
+        for i in range(nO):
+            for j in range(i + 1, nO):
+                for t in range(CT):
+                    iou = pose_iou(fut[i + 1, t], lw[i + 1], fut[j + 1, t], lw[j + 1])
+                    if np.isnan(iou):
+                        continue
+                    margin = min(margin, abs(iou - IOU_THRESH))
+                    if iou > IOU_THRESH:
+                        marks[i] = 1
+        I.update(num_coll_veh=int(marks.sum()), num_traj_veh=nO)
+        if raster is not None:
+            valid = ~np.isnan(fut[:, :CT].astype(np.float64).sum(-1))
+            cnt = valid.sum(1)
+            tot = int(cnt.sum())
+            L = W = 0
+            env = np.zeros((n,), dtype=np.int64)
+            if tot > 0:
+                sl = sw = 0.0
+                for a in range(n):
+                    sl += float(cnt[a]) * float(lw[a, 0])
+                    sw += float(cnt[a]) * float(lw[a, 1])
+                ml, mw = sl / tot, sw / tot
+                sdx = 0.0
+                for v in np.asarray(dx, dtype=np.float64).reshape(-1):
+                    sdx += float(v)
+                mdx = sdx / np.asarray(dx).size
+                L, W = int(np.rint(ml / mdx)), int(np.rint(mw / mdx))
+                for q in (ml / mdx, mw / mdx):
+                    margin_grid = min(margin_grid, abs(q - np.floor(q) - 0.5))
+                Dd.update(env_mean_l=ml, env_mean_w=mw)
+                for a in range(n):
+                    for t in range(CT):
+                        if not valid[a, t]:
+                            continue
+                        on = drivable_count(raster[mapix, 0], dx[mapix], fut[a, t], lw[a], L, W)
+                        margin_frac = min(margin_frac, abs(on - 0.95 * L * W))
+                        if f32(on) / f32(L * W) < f32(1.0 - 0.05):
+                            env[a] = 1
+            I.update(env_coll_atk=int(env[atk]), env_coll_others=int(sum(env[a] for a in others)), env_L=L, env_W=W, env_frames=tot)
+    # accelerations
+    for who, agents in (('atk', [atk]), ('other', others)):
+        cnt, series = 0, [[], [], []]
+        if CT > 2:
+            for a in agents:
+                for c, s in enumerate(accels(fut[a], CT, dt)):
+                    series[c] += list(s)
+            cnt = len(series[0])
+        I[who + '_accel_cnt'] = cnt
+        for c, suffix in enumerate(('accel', 'accel_fwd', 'accel_lat')):
+            if cnt > 0 and who == 'other':
+                # the kernel adds every agent's own sum, then the agents in order
+                tot = 0.0
+                for a in agents:
+                    tot += seq_sum(accels(fut[a], CT, dt)[c])
+                Dd['%s_%s_sum' % (who, suffix)] = tot
+            else:
+                Dd['%s_%s_sum' % (who, suffix)] = seq_sum(series[c]) if cnt > 0 else nan
+            Dd['%s_%s_max' % (who, suffix)] = nan_max([nan_max(accels(fut[a], CT, dt)[c]) for a in agents]) if cnt > 0 else nan
+            A['%s_%s_sum' % (who, suffix)] = float(np.abs(series[c]).sum()) if cnt > 0 else nan
+    # latents
+    I['ll_other_cnt'] = -1
+    Dd.update(ll_atk=nan, ll_other_sum=nan)
+    if z is not None:
+        z64, m64, v64 = [np.asarray(v, dtype=f32).astype(np.float64) for v in (z, mu, var)]
+        terms = -np.log(np.sqrt(v64)) - LOG_SQRT_2PI - ((z64 - m64) * (z64 - m64)) / (2.0 * v64)
+        ll = [seq_sum(row) for row in terms]
+        ab = np.abs(terms).sum(1)
+        I['ll_other_cnt'] = len(others)
+        Dd['ll_atk'], A['ll_atk'] = ll[atk], float(ab[atk])
+        if others:
+            Dd['ll_other_sum'], A['ll_other_sum'] = seq_sum([ll[a] for a in others]), float(sum(ab[a] for a in others))
+    # planner fit
+    I['fit_cnt'] = -1
+    Dd.update(fit_pos_sum=nan, fit_ang_rad_sum=nan, fit_ang_deg_sum=nan)
+    if fit is not None:
+        g, q = fut[0, :CT].astype(np.float64), np.asarray(fit, dtype=f32)[:CT].astype(np.float64)
+        e = g[:, :2] - q[:, :2]
+        pos = np.sqrt(e[:, 0] * e[:, 0] + e[:, 1] * e[:, 1])
+        gn, qn = np.sqrt(g[:, 2] * g[:, 2] + g[:, 3] * g[:, 3]), np.sqrt(q[:, 2] * q[:, 2] + q[:, 3] * q[:, 3])
+        dot = np.clip((g[:, 2] / gn) * (q[:, 2] / qn) + (g[:, 3] / gn) * (q[:, 3] / qn), -1.0, 1.0)
+        ang = np.arccos(dot)
+        I['fit_cnt'] = CT
+        Dd.update(fit_pos_sum=seq_sum(pos), fit_ang_rad_sum=seq_sum(ang), fit_ang_deg_sum=seq_sum(ang * (180.0 / np.pi)))
+        A.update(fit_pos_sum=Dd['fit_pos_sum'], fit_ang_rad_sum=Dd['fit_ang_rad_sum'], fit_ang_deg_sum=Dd['fit_ang_deg_sum'])
+    # features
+    I.update(feat_status=-1, fine_t=-1, fine_agt=-1, lr_coll_t=-1)
+    for k in ('hvec_x', 'hvec_y', 'angvec_x', 'angvec_y', 'h', 'ang', 'rel_s'):
+        Dd[k] = nan
+    if want_feat:
+        fine = interp32(fut, FEAT_SCALE)
+        TO = T * FEAT_SCALE
+        ftimes = np.full((nO,), TO, dtype=np.int64)
+        for al in range(nO):
+            for j in range(TO):
+                iou = pose_iou(fine[0, j], lw[0], fine[al + 1, j], lw[al + 1])
+                if np.isnan(iou):
+                    continue
+                margin = min(margin, abs(iou - IOU_THRESH))
+                if iou > IOU_THRESH:
+                    ftimes[al] = j
+                    break
+        if (ftimes < TO).any():
+            ft, fa = int(ftimes.min()), int(ftimes.argmin())
+            g, u = fine[0, ft].astype(np.float64), fine[fa + 1, ft].astype(np.float64)
+            hc, hs = u[2] * g[2] + u[3] * g[3], u[3] * g[2] - u[2] * g[3]
+            ddx, ddy = u[0] - g[0], u[1] - g[1]
+            lx, ly = g[2] * ddx + g[3] * ddy, -g[3] * ddx + g[2] * ddy
+            ln = np.sqrt(lx * lx + ly * ly)
+            lr = int((ft * (dt / float(FEAT_SCALE))) / dt)
+            f1 = lr if lr > 0 else lr + 1
+            o = fut.astype(np.float64)
+            rx = (o[0, f1, 0] - o[0, f1 - 1, 0]) / dt - (o[fa + 1, f1, 0] - o[fa + 1, f1 - 1, 0]) / dt
+            ry = (o[0, f1, 1] - o[0, f1 - 1, 1]) / dt - (o[fa + 1, f1, 1] - o[fa + 1, f1 - 1, 1]) / dt
+            I.update(feat_status=0, fine_t=ft, fine_agt=fa, lr_coll_t=lr)
+            Dd.update(hvec_x=hc, hvec_y=hs, angvec_x=lx / ln, angvec_y=ly / ln, h=np.arctan2(hs, hc), ang=np.arctan2(ly / ln, lx / ln),
+                      rel_s=np.sqrt(rx * rx + ry * ry))
+        else:
+            I['feat_status'] = 1
+    return dict(i=I, d=Dd, abs=A, margin_iou=margin, margin_frac=margin_frac, margin_grid=margin_grid)
+
+
+def kmeans_step(x, centers):
+    """labels (lowest index on equal distance), mind, sums, counts, inertia -- the sums in ANY order (compare with a tolerance)."""
+    x, c = np.asarray(x, dtype=np.float64), np.asarray(centers, dtype=np.float64)
+    d = np.zeros((x.shape[0], c.shape[0]))
+    for f in range(x.shape[1]):
+        e = x[:, f:f + 1] - c[None, :, f]
+        d += e * e
+    labels = d.argmin(1)
+    mind = d[np.arange(x.shape[0]), labels]
+    sums = np.stack([x[labels == j].sum(0) if (labels == j).any() else np.zeros((x.shape[1],)) for j in range(c.shape[0])])
+    counts = np.asarray([(labels == j).sum() for j in range(c.shape[0])])
+    srt = np.sort(d, axis=1)
+    gap = float((srt[:, 1] - srt[:, 0]).min()) if c.shape[0] > 1 else np.inf
+    return labels, mind, sums, counts, float(mind.sum()), gap
