@@ -515,6 +515,33 @@ int strive_scenario_eval_metrics(const float* fut, const int32_t* ptr, const flo
                                  int32_t lin_max, const int32_t* want_feat, int32_t B, int32_t NA, int32_t T, int32_t* out_i,
                                  double* out_d, int32_t* status, strive_stream_t stream);
 
+/* Traffic-model evaluation metrics (reference src/test_traffic.py:84-277 with compute_err, compute_disp_err,
+ * compute_coll_rate_env and compute_coll_rate_veh of reference src/losses/traffic_model.py:120-164, :297-364, :366-419,
+ * :465-545) for ONE prediction set of B scenes in one host call without a host synchronisation; float64 on the fp32 inputs,
+ * one workgroup per scene (up to 8 with many samples: a scene's (agent, sample) flags are dealt out, each has one owner),
+ * preceded by a one-workgroup launch that forms the batch-wide sampling grid when env is asked for.
+ *   pred (NA,NS,T,4), gt (NA,Tg,6) and lw (NA,2) NORMALISED, unnormalised in fp32 as v * std + mean (MeanStdNormalizer,
+ *   reference src/datasets/utils.py:75-90) with the four host arrays; vis (NA,Tg) fp32; ptr (B+1) agent offsets, the ego first;
+ *   map + mapix (B) + lin_tab / lin_max as for strive_scenario_eval_metrics (env only); groups = 1 err | 2 disp | 4 veh |
+ *   8 env | 16 use the caller's grid_i instead of forming it; env_ego_only as the reference's ego_only.
+ *   err : pos_err, ang_err (NA,Tg) of sample 0, NaN where vis != 1, degrees (needs T == Tg)
+ *   disp: (B,5) pos_minADE, pos_minFDE, ang_minADE, ang_minFDE, APD of the scene's ego over min(T, Tg) steps (APD NaN for NS 1)
+ *   veh : did_veh (NA,NS) int32, agent i overlaps (IoU > 0.02) an agent j > i of its scene at some step; NaN frames never hit
+ *   env : did_map (B,NS) with env_ego_only else (NA,NS) int32, some valid frame has fp32(count) / fp32(L W) < fp32(0.95) on
+ *         raster layer 0 (check_on_layer, reference src/datasets/nuscenes_utils.py:266-298); L = round(mean_l / mean(dx)), W
+ *         likewise over the valid (agent, sample, step) rows of the whole call (ego rows only with env_ego_only);
+ *         grid_i (3) = L, W, valid rows (clamped); grid_d (2) = the two ratios before rounding (NaN without a valid row)
+ *   status (B) int32: 0 = written; 2 = offsets leave the arrays; 3 = map index out of range; 4 = the grid is outside
+ *         1..lin_max (outputs untouched for every non-zero status).  A group that is not asked for leaves its outputs
+ *         untouched and may pass NULL for them.
+ * Given the grid, a scene's outputs are bit-identical whatever else is in the batch. */
+int strive_traffic_eval_metrics(const float* pred, const float* gt, const float* vis, const int32_t* ptr, const float* lw,
+                                const float* state_mean4_host, const float* state_std4_host, const float* att_mean2_host,
+                                const float* att_std2_host, const StriveMap* map, const int32_t* mapix, const float* lin_tab,
+                                int32_t lin_max, int32_t groups, int32_t env_ego_only, int32_t B, int32_t NA, int32_t NS,
+                                int32_t T, int32_t Tg, double* pos_err, double* ang_err, double* disp, int32_t* did_veh,
+                                int32_t* did_map, int32_t* grid_i, double* grid_d, int32_t* status, strive_stream_t stream);
+
 /* One Lloyd step of k-means on x (N,F) float64 with centers (k,F), F = 1..8, k = 1..64 (the clustering of reference
  * src/cluster_scenarios.py, which calls scikit-learn's KMeans on the host): labels (N) = nearest centre, the lowest index on
  * equal squared distance; mind (N) that distance; sums (k,F) and counts (k) per cluster; inertia (1) = sum of mind.  Two

@@ -1033,6 +1033,350 @@ extern "C" int strive_scenario_eval_metrics(const float* fut, const int32_t* ptr
 }
 
 // =============================================================================================
+// Traffic-model evaluation (reference src/test_traffic.py:84-277 and the metric functions it calls in
+// src/losses/traffic_model.py) for ONE prediction set pred (NA,NS,T,4) of B scenes in one host call without a host
+// synchronisation: float64 on the fp32 inputs, one workgroup per scene (up to 8 with many samples, each owning whole items).  Poses, ground truth and vehicle sizes arrive
+// NORMALISED and are unnormalised in fp32 exactly as MeanStdNormalizer.unnormalize does (v * std + mean, src/datasets/utils.py:
+// 75-90), so pixel selection and box corners start from the fp32 values the reference sees.  Four optional groups (`groups`
+// bits 1, 2, 4, 8); a group that is not asked for leaves its outputs untouched:
+//   err  (compute_err, :120-164, sample 0, T == Tg): pos_err / ang_err (NA,Tg), NaN where vis != 1; unit headings, the dot
+//        product clamped to [-1, 1] before acos, degrees.
+//   disp (compute_disp_err, :297-364): per scene for its ego ptr[b] over Tc = min(T, Tg): pos_minADE, pos_minFDE, ang_minADE,
+//        ang_minFDE (a NaN sample makes the minimum NaN, as torch.min does) and APD = 2 sum_{s<s'} sum_t |p_s - p_s'| /
+//        (NS (NS-1) Tc), 0/0 = NaN for NS = 1.  One thread walks a sample's steps in order; the (s, s', t) terms are strided over
+//        the workgroup and the 256 partial sums added by one thread in thread order: no NS x NS x T array anywhere.
+//   veh  (compute_coll_rate_veh, :465-545): did_collide_veh (NA,NS): agent i overlaps (IoU > 0.02) some agent j > i of the same
+//        scene at some step of sample s; a frame with a NaN in either pose is no hit.  The reference's early exits make
+//        coll_count the number of set flags and the set does not depend on the order of evaluation: ONE WAVE owns a flag, its
+//        lanes stride over (j, t) and vote, lane 0 writes -- no atomics.
+//   env  (compute_coll_rate_env, :366-419 -> check_on_layer, src/datasets/nuscenes_utils.py:266-298): did_collide_map (B,NS)
+//        with env_ego_only, else (NA,NS): some valid frame has fp32(count) / fp32(L W) < fp32(0.95) on raster layer 0.  One
+//        wave owns a flag, walks the frames in order, its lanes stride over the L x W samples (crop_dev.h: fp32 grid, float64
+//        divide, round half even, outside -> pixel (0,0)) and add their integer counts.  The grid couples the batch: L =
+//        round(mean_l / mean(dx)), W likewise, mean over the valid (agent, sample, step) rows of the whole call (ego rows only
+//        with env_ego_only), mean(dx) over all entries of the map's dx.  traffic_eval_grid_kernel (one workgroup, launched
+//        first) forms it in float64: a thread adds count * size for the agents tid, tid + 256, ... in that order, one thread adds
+//        the 256 partial sums in thread order.  grid_i = (L, W, valid rows clamped to int32), grid_d = the two ratios before
+//        rounding (NaN without a valid row: then there is no grid and no collision).  With bit 16 of `groups` the caller's grid_i
+//        is used as given and the first launch is skipped.
+//   status (B): 0 written; 2 agent offsets leave the arrays or n < 1; 3 map index out of range; 4 the grid is outside
+//        1..lin_max along an axis (every scene of the call).  Outputs are untouched for a scene with a non-zero status; rows of
+//        such a scene still enter the grid means when they can be addressed (with env_ego_only: when its offsets are valid).
+// Given the grid, a scene's outputs are bit-identical whatever else is in the batch.
+// =============================================================================================
+#define TE_ERR 1
+#define TE_DISP 2
+#define TE_VEH 4
+#define TE_ENV 8
+#define TE_GRID_GIVEN 16
+#define TE_NT 256
+
+struct TrafficEvalArgs {
+    const float* pred; const float* gt; const float* vis; const int32_t* ptr; const float* lw;
+    float sm[4], ss[4], am[2], asd[2];
+    const int32_t* mapix; const float* lin_tab; int lin_max;
+    int groups, ego_only;
+    int B, NA, NS, T, Tg;
+    double* pos_err; double* ang_err; double* disp; int32_t* did_veh; int32_t* did_map;
+    int32_t* grid_i; double* grid_d; int32_t* status;
+};
+
+__device__ __forceinline__ void te_pose(const TrafficEvalArgs& A, const float* p, float u[4]) {
+    for (int c = 0; c < 4; ++c) u[c] = unnorm1(p[c], A.sm[c], A.ss[c]);
+}
+
+__device__ __forceinline__ void te_lw(const TrafficEvalArgs& A, int ag, float u[2]) {
+    u[0] = unnorm1(A.lw[(size_t)ag * 2 + 0], A.am[0], A.asd[0]);
+    u[1] = unnorm1(A.lw[(size_t)ag * 2 + 1], A.am[1], A.asd[1]);
+}
+
+// position error (m) and angle between the unit headings (degrees) of two fp32 poses
+__device__ __forceinline__ void te_errs(const float* g, const float* p, double& pos, double& deg) {
+#pragma clang fp contract(off)
+    const double ex = (double)g[0] - (double)p[0], ey = (double)g[1] - (double)p[1];
+    pos = sqrt(ex * ex + ey * ey);
+    const double gx = (double)g[2], gy = (double)g[3], qx = (double)p[2], qy = (double)p[3];
+    const double gn = sqrt(gx * gx + gy * gy), qn = sqrt(qx * qx + qy * qy);
+    double dot = (gx / gn) * (qx / qn) + (gy / gn) * (qy / qn);
+    dot = dot < -1.0 ? -1.0 : (dot > 1.0 ? 1.0 : dot);
+    deg = acos(dot) * (180.0 / 3.14159265358979323846);
+}
+
+// torch.min over values that may hold NaN: NaN wins
+__device__ __forceinline__ double te_min(double m, double v) { return (m != m || v != v) ? (m + v) : (v < m ? v : m); }
+
+__global__ __launch_bounds__(TE_NT) void traffic_eval_grid_kernel(TrafficEvalArgs A, StriveMap map) {
+#pragma clang fp contract(off)
+    __shared__ long long s_cnt[TE_NT];
+    __shared__ double s_l[TE_NT], s_w[TE_NT];
+    const int tid = threadIdx.x;
+    const int items = A.ego_only ? A.B : A.NA;
+    const size_t frames = (size_t)A.NS * A.T;
+    long long cnt = 0;
+    double sl = 0.0, sw = 0.0;
+    for (int k = tid; k < items; k += TE_NT) {
+        int a = k;
+        if (A.ego_only) {
+            const int a0 = A.ptr[k], a1 = A.ptr[k + 1];
+            if (a0 < 0 || a1 <= a0 || a1 > A.NA) continue;
+            a = a0;
+        }
+        const float* p = A.pred + (size_t)a * frames * 4;
+        int c = 0;
+        for (size_t f = 0; f < frames; ++f) {
+            float u[4];
+            te_pose(A, p + f * 4, u);
+            c += se_nan4(u) ? 0 : 1;
+        }
+        if (c > 0) {
+            float lwu[2];
+            te_lw(A, a, lwu);
+            cnt += c;
+            sl += (double)c * (double)lwu[0];
+            sw += (double)c * (double)lwu[1];
+        }
+    }
+    s_cnt[tid] = cnt;
+    s_l[tid] = sl;
+    s_w[tid] = sw;
+    __syncthreads();
+    if (tid != 0) return;
+    const double kNaN = __longlong_as_double(0x7ff8000000000000ll);
+    long long tot = 0;
+    double tl = 0.0, tw = 0.0, sdx = 0.0;
+    for (int i = 0; i < TE_NT; ++i) {
+        tot += s_cnt[i];
+        tl += s_l[i];
+        tw += s_w[i];
+    }
+    for (int m = 0; m < map.M * 2; ++m) sdx += map.dx[m];
+    const double mdx = sdx / (double)(map.M * 2);
+    double rl = kNaN, rw = kNaN;
+    int L = 0, W = 0;
+    if (tot > 0) {
+        rl = (tl / (double)tot) / mdx;
+        rw = (tw / (double)tot) / mdx;
+        const double ql = rint(rl), qw = rint(rw);
+        // (saturating: a grid the table cannot serve is reported, and refused by every scene, not sampled)
+        L = (ql >= -1.0e9 && ql <= 1.0e9) ? (int)ql : -1;
+        W = (qw >= -1.0e9 && qw <= 1.0e9) ? (int)qw : -1;
+    }
+    A.grid_i[0] = L;
+    A.grid_i[1] = W;
+    A.grid_i[2] = tot > 0x7fffffffll ? 0x7fffffff : (int)tot;
+    A.grid_d[0] = rl;
+    A.grid_d[1] = rw;
+}
+
+__global__ __launch_bounds__(TE_NT) void traffic_eval_kernel(TrafficEvalArgs A, StriveMap map) {
+#pragma clang fp contract(off)
+    __shared__ double s_red[TE_NT];
+    __shared__ double s_min[4][TE_NT];
+    const double kNaN = __longlong_as_double(0x7ff8000000000000ll), kInf = __longlong_as_double(0x7ff0000000000000ll);
+    // gridDim.y workgroups share a scene: the (agent, step) items of err and the wave-owned flags of veh / env are dealt out across
+    // them (every item still has exactly one owner, so the outputs do not depend on gridDim.y); disp and the status belong to part 0
+    const int b = blockIdx.x, part = blockIdx.y, nparts = gridDim.y, tid = threadIdx.x, lane = tid & 63;
+    const int wave = part * (TE_NT / 64) + (tid >> 6), nwaves = nparts * (TE_NT / 64);
+    const int T = A.T, Tg = A.Tg, NS = A.NS;
+    const int a0 = A.ptr[b], a1 = A.ptr[b + 1], n = a1 - a0;
+    const bool env = (A.groups & TE_ENV) != 0;
+    int st = 0, L = 0, W = 0, rows = 0;
+    if (a0 < 0 || n <= 0 || a1 > A.NA) st = 2;
+    else if (env && (A.mapix[b] < 0 || A.mapix[b] >= map.M)) st = 3;
+    else if (env) {
+        L = A.grid_i[0];
+        W = A.grid_i[1];
+        rows = A.grid_i[2];
+        if (rows > 0 && (L < 1 || L > A.lin_max || W < 1 || W > A.lin_max)) st = 4;
+    }
+    if (st != 0) {
+        if (tid == 0 && part == 0) A.status[b] = st;
+        return;
+    }
+
+    // ---- err: sample 0 of every agent against the ground truth ----
+    if (A.groups & TE_ERR) {
+        for (int e = part * TE_NT + tid; e < n * Tg; e += nparts * TE_NT) {
+            const int a = e / Tg, t = e - a * Tg;
+            const size_t ag = (size_t)(a0 + a), o = ag * Tg + t;
+            double pos = kNaN, deg = kNaN;
+            if (A.vis[o] == 1.0f) {
+                float g[4], p[4];
+                te_pose(A, A.gt + o * 6, g);
+                te_pose(A, A.pred + (ag * NS * T + t) * 4, p);
+                te_errs(g, p, pos, deg);
+            }
+            A.pos_err[o] = pos;
+            A.ang_err[o] = deg;
+        }
+    }
+
+    // ---- disp: the ego's samples against its ground truth over the common horizon ----
+    if ((A.groups & TE_DISP) && part == 0) {
+        const int Tc = T < Tg ? T : Tg;
+        const float* gt = A.gt + (size_t)a0 * Tg * 6;
+        const float* pr = A.pred + (size_t)a0 * NS * T * 4;
+        double m[4] = {kInf, kInf, kInf, kInf};
+        for (int s = tid; s < NS; s += TE_NT) {
+            double sd = 0.0, sa = 0.0, pos = 0.0, deg = 0.0;
+            for (int t = 0; t < Tc; ++t) {
+                float g[4], p[4];
+                te_pose(A, gt + (size_t)t * 6, g);
+                te_pose(A, pr + ((size_t)s * T + t) * 4, p);
+                te_errs(g, p, pos, deg);
+                sd += pos;
+                sa += deg;
+            }
+            m[0] = te_min(m[0], sd / (double)Tc);
+            m[1] = te_min(m[1], pos);
+            m[2] = te_min(m[2], sa / (double)Tc);
+            m[3] = te_min(m[3], deg);
+        }
+        double acc = 0.0;
+        const int per = NS * Tc;
+        for (int e = tid; e < NS * per; e += TE_NT) {
+            const int s = e / per, r = e - s * per, s2 = r / Tc, t = r - s2 * Tc;
+            if (s2 <= s) continue;
+            float p[4], q[4];
+            te_pose(A, pr + ((size_t)s * T + t) * 4, p);
+            te_pose(A, pr + ((size_t)s2 * T + t) * 4, q);
+            const double ex = (double)p[0] - (double)q[0], ey = (double)p[1] - (double)q[1];
+            acc += sqrt(ex * ex + ey * ey);
+        }
+        s_red[tid] = acc;
+        for (int c = 0; c < 4; ++c) s_min[c][tid] = m[c];
+        __syncthreads();
+        if (tid == 0) {
+            double sum = 0.0;
+            for (int i = 0; i < TE_NT; ++i) sum += s_red[i];
+            for (int c = 0; c < 4; ++c) {
+                double v = s_min[c][0];
+                for (int i = 1; i < TE_NT; ++i) v = te_min(v, s_min[c][i]);
+                A.disp[(size_t)b * 5 + c] = v;
+            }
+            A.disp[(size_t)b * 5 + 4] = (2.0 * sum) / ((double)NS * (double)(NS - 1) * (double)Tc);
+        }
+    }
+
+    // ---- veh: one wave per (agent, sample) flag ----
+    if (A.groups & TE_VEH) {
+        for (int f = wave; f < n * NS; f += nwaves) {
+            const int i = f / NS, s = f - i * NS;
+            const int items = (n - 1 - i) * T;
+            float lwi[2];
+            te_lw(A, a0 + i, lwi);
+            const float* pi = A.pred + ((size_t)(a0 + i) * NS + s) * T * 4;
+            bool hit = false;
+            for (int base = 0; base < items && !hit; base += 64) {
+                const int e = base + lane;
+                bool h = false;
+                if (e < items) {
+                    const int dj = e / T, t = e - dj * T, j = i + 1 + dj;
+                    float u[4], v[4], lwj[2];
+                    te_pose(A, pi + (size_t)t * 4, u);
+                    te_pose(A, A.pred + (((size_t)(a0 + j) * NS + s) * T + t) * 4, v);
+                    if (!se_nan4(u) && !se_nan4(v)) {
+                        te_lw(A, a0 + j, lwj);
+                        h = se_iou(u, lwi, v, lwj) > PLAN_EVAL_IOU_THRESH;
+                    }
+                }
+                hit = __ballot(h ? 1 : 0) != 0ull;
+            }
+            if (lane == 0) A.did_veh[(size_t)(a0 + i) * NS + s] = hit ? 1 : 0;
+        }
+    }
+
+    // ---- env: one wave per (agent, sample) flag, frames in order, lanes over the sampling grid ----
+    if (env) {
+        const int nag = A.ego_only ? 1 : n, m = A.mapix[b], cells = L * W;
+        const float* lin_l = A.lin_tab + (size_t)L * (L > 0 ? L - 1 : 0) / 2;     // linspace(-1, 1, k) starts at k (k - 1) / 2
+        const float* lin_w = A.lin_tab + (size_t)W * (W > 0 ? W - 1 : 0) / 2;
+        const float thresh = (float)(1.0 - 0.05), area = (float)cells;
+        for (int f = wave; f < nag * NS; f += nwaves) {
+            const int a = f / NS, s = f - a * NS, ag = a0 + a;
+            float lwa[2];
+            te_lw(A, ag, lwa);
+            bool hit = false;
+            for (int t = 0; rows > 0 && t < T && !hit; ++t) {
+                float u[4];
+                te_pose(A, A.pred + (((size_t)ag * NS + s) * T + t) * 4, u);
+                if (se_nan4(u)) continue;
+                CropFrame fr;
+                fr.x = u[0]; fr.y = u[1]; fr.hc = u[2]; fr.hs = u[3];
+                set_crop_scale(fr, map.dx[m * 2 + 0], map.dx[m * 2 + 1]);
+                fr.H = map.H;
+                fr.W = map.W;
+                fr.base = map.raster + (size_t)m * map.C * map.H * map.W;      // layer 0
+                int on = 0;
+                for (int c = lane; c < cells; c += 64) {
+                    const int i = c / W, j = c - i * W;
+                    const float lwise = __fmul_rn(lin_l[i], lwa[0]) * 0.5f, wwise = __fmul_rn(lin_w[j], lwa[1]) * 0.5f;
+                    int px, py;
+                    float gx, gy;
+                    crop_world(fr, lwise, wwise, gx, gy);
+                    world_to_pixel(fr, gx, gy, px, py);
+                    on += fr.base[(size_t)py * map.W + px] != 0 ? 1 : 0;
+                }
+                for (int k = 32; k >= 1; k >>= 1) on += __shfl_xor(on, k);
+                hit = __fdiv_rn((float)on, area) < thresh;
+            }
+            if (lane == 0) A.did_map[(size_t)(A.ego_only ? b : ag) * NS + s] = hit ? 1 : 0;
+        }
+    }
+    if (tid == 0 && part == 0) A.status[b] = 0;
+}
+
+extern "C" int strive_traffic_eval_metrics(const float* pred, const float* gt, const float* vis, const int32_t* ptr, const float* lw,
+                                           const float* state_mean4_host, const float* state_std4_host,
+                                           const float* att_mean2_host, const float* att_std2_host, const StriveMap* map,
+                                           const int32_t* mapix, const float* lin_tab, int32_t lin_max, int32_t groups,
+                                           int32_t env_ego_only, int32_t B, int32_t NA, int32_t NS, int32_t T, int32_t Tg,
+                                           double* pos_err, double* ang_err, double* disp, int32_t* did_veh, int32_t* did_map,
+                                           int32_t* grid_i, double* grid_d, int32_t* status, strive_stream_t stream) {
+    STRIVE_CHECK_ARG(pred && ptr && lw && status, "null argument");
+    STRIVE_CHECK_ARG(state_mean4_host && state_std4_host && att_mean2_host && att_std2_host, "null normaliser statistics");
+    STRIVE_CHECK_ARG((groups & ~(TE_ERR | TE_DISP | TE_VEH | TE_ENV | TE_GRID_GIVEN)) == 0, "unknown metric group");
+    STRIVE_CHECK_ARG(NA >= 0 && NS >= 1 && T >= 1 && Tg >= 1, "bad sizes");
+    STRIVE_CHECK_ARG((long long)NA * NS < 0x7fffffffll && (long long)NA * (T > Tg ? T : Tg) < 0x7fffffffll &&
+                     (long long)NS * NS * (T < Tg ? T : Tg) < 0x7fffffffll, "sizes exceed the 32-bit item counts");
+    STRIVE_CHECK_ARG(!(groups & TE_ERR) || (gt && vis && pos_err && ang_err && T == Tg), "err needs gt, vis, its outputs and T == Tg");
+    STRIVE_CHECK_ARG(!(groups & TE_DISP) || (gt && disp), "disp needs gt and its output");
+    STRIVE_CHECK_ARG(!(groups & TE_VEH) || did_veh, "veh needs its output");
+    if (groups & TE_ENV) {
+        STRIVE_CHECK_ARG(map && mapix && lin_tab && lin_max >= 1 && did_map && grid_i && grid_d, "env needs a map, mapix, the linspace table and its outputs");
+        STRIVE_CHECK_ARG(map->raster && map->dx && map->M >= 1 && map->C >= 1 && map->H >= 1 && map->W >= 1, "bad map");
+    }
+    if (B <= 0) return 0;
+    TrafficEvalArgs A;
+    A.pred = pred; A.gt = gt; A.vis = vis; A.ptr = ptr; A.lw = lw;
+    for (int c = 0; c < 4; ++c) {
+        A.sm[c] = state_mean4_host[c];
+        A.ss[c] = state_std4_host[c];
+    }
+    for (int c = 0; c < 2; ++c) {
+        A.am[c] = att_mean2_host[c];
+        A.asd[c] = att_std2_host[c];
+    }
+    A.mapix = mapix; A.lin_tab = lin_tab; A.lin_max = lin_max;
+    A.groups = groups; A.ego_only = env_ego_only ? 1 : 0;
+    A.B = B; A.NA = NA; A.NS = NS; A.T = T; A.Tg = Tg;
+    A.pos_err = pos_err; A.ang_err = ang_err; A.disp = disp; A.did_veh = did_veh; A.did_map = did_map;
+    A.grid_i = grid_i; A.grid_d = grid_d; A.status = status;
+    StriveMap m;
+    memset(&m, 0, sizeof(m));
+    if (map) m = *map;
+    if ((groups & TE_ENV) && !(groups & TE_GRID_GIVEN)) {
+        hipLaunchKernelGGL(traffic_eval_grid_kernel, dim3(1), dim3(TE_NT), 0, (hipStream_t)stream, A, m);
+        STRIVE_CHECK_LAUNCH();
+    }
+    // latency-bound: a scene's wave-owned flags (n x NS of them) spread over up to 8 workgroups
+    const int parts = NS >= 15 ? 8 : (NS >= 2 ? (NS + 1) / 2 : 1);
+    hipLaunchKernelGGL(traffic_eval_kernel, dim3(B, parts), dim3(TE_NT), 0, (hipStream_t)stream, A, m);
+    STRIVE_CHECK_LAUNCH();
+    return 0;
+}
+
+// =============================================================================================
 // One Lloyd step of k-means on N x F float64 features (the clustering of reference src/cluster_scenarios.py, whose
 // KMeans.fit / .predict run scikit-learn on the host): every row's nearest centre (squared distance summed over the
 // features in order, the lowest index on equal distance), then per-cluster sums and counts and the inertia.  No atomics on

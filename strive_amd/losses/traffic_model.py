@@ -114,6 +114,28 @@ class TrafficModelLoss(nn.Module):
         return out
 
 
+    def dense_terms(self, scene_graph, pred):
+        """``forward`` without its compaction, for loops that must not synchronise (strive_amd/test_traffic.py): the same terms with
+        ``recon_loss`` DENSE, (NA,T), beside the mask of the frames ``forward`` keeps.  ``forward`` selects the visible frames
+        through an index built with ``torch.nonzero`` -- a read-back the first time it sees a batch object; here the reconstruction
+        mean is a masked sum over all frames divided by the number of visible ones.  Returns ``(terms, masks)``: ``terms`` in
+        ``forward``'s key order, ``masks[key]`` where only part of ``terms[key]`` counts.  Only for predictions without
+        ``future_samp`` (the prior-sample collision terms need ``forward``)."""
+        if 'future_samp' in pred:
+            raise ValueError('dense_terms covers the reconstruction and KL terms only; call forward for the collision terms')
+        w = self.loss_weights
+        fp = pred['future_pred']
+        if tuple(fp.shape[:2]) != tuple(scene_graph.future_vis.shape[:2]):
+            raise IndexError('future_pred %s does not match future_vis %s' % (tuple(fp.shape), tuple(scene_graph.future_vis.shape)))
+        vis = scene_graph.future_vis == 1.0
+        recon = -log_normal(fp, scene_graph.future_gt[..., :4], torch.ones_like(fp))
+        pm, pv = pred['prior_out']
+        qm, qv = pred['posterior_out']
+        kl = kl_normal(qm, qv, pm, pv)
+        rmean = torch.where(vis, recon, torch.zeros_like(recon)).sum() / vis.sum()
+        loss = w['recon'] * rmean + w['kl'] * kl.mean()
+        return {'recon_loss': recon, 'kl_loss': kl, 'loss': loss.view((1,))}, {'recon_loss': vis}
+
     def compute_err(self, scene_graph, pred, normalizer):
         """Interpretable errors the training / test loops log (reference :120-164): position error (m) and heading error
         (degrees) per visible frame, NLL and Mahalanobis distance of the posterior mean under the prior per agent."""

@@ -215,7 +215,7 @@ def _split_like(flat, params):
 
 class SceneInfo(object):
     def __init__(self, ptr, device):
-        self.ptr = ptr.to(device)
+        self.ptr = params.upload(ptr, device)
         self.ptr_cpu = ptr.cpu().clone()
         self.ei_sig = None
         self.ptr_sig = None
@@ -230,12 +230,12 @@ class SceneInfo(object):
             per_agent = torch.repeat_interleave(sz, sz)
             self.pair_off[1:] = torch.cumsum(per_agent, 0)[:-1].to(torch.int32)
         self.P = int((sz * sz).sum())
-        self.pair_off = self.pair_off.to(device)
+        self.pair_off = params.upload(self.pair_off, device)
 
     def pack(self, NS):
         p = self._packs.get(NS)
         if p is None:
-            p = params.pack_scenes(self.ptr.cpu(), NS, self.device)
+            p = params.pack_scenes(self.ptr_cpu, NS, self.device)
             self._packs[NS] = p
         return p
 
@@ -289,6 +289,27 @@ def scene_info(scene_graph):
         ei = scene_graph.edge_index.cpu()
         exp = _expected_clique_keys(ptr.cpu(), info.NA)
         got = ei[0] * info.NA + ei[1]
+        if got.shape[0] != exp.shape[0] or not torch.equal(torch.sort(got)[0], torch.sort(exp)[0]):
+            raise NotImplementedError('strive_amd message passing requires per-scene fully connected graphs without '
+                                      'self loops (what the reference dataset builds); got a different edge_index')
+    scene_graph.__dict__['_strive_scene_info'] = info
+    return info
+
+
+def prime_scene_info(scene_graph, ptr_cpu, ei_cpu=None):
+    """``scene_info`` for a graph whose tensors have just been copied to the device, from the HOST copies of its ``ptr`` and
+    ``edge_index``: the same validation and the same SceneInfo, without reading the structure back from the device (which is a
+    host synchronisation per fresh batch).  The caller vouches that ``ptr_cpu`` / ``ei_cpu`` hold what ``scene_graph`` holds."""
+    info = SceneInfo(ptr_cpu, scene_graph.past.device)
+    ei = scene_graph.edge_index if 'edge_index' in scene_graph else None
+    ptr = scene_graph.ptr
+    info.ei_sig = None if ei is None else (ei.data_ptr(), ei._version, tuple(ei.shape))
+    info.ptr_sig = (ptr.data_ptr(), ptr._version, tuple(ptr.shape))
+    if ei is not None:
+        if ei_cpu is None:
+            raise ValueError('prime_scene_info needs the host copy of edge_index')
+        exp = _expected_clique_keys(ptr_cpu, info.NA)
+        got = ei_cpu[0] * info.NA + ei_cpu[1]
         if got.shape[0] != exp.shape[0] or not torch.equal(torch.sort(got)[0], torch.sort(exp)[0]):
             raise NotImplementedError('strive_amd message passing requires per-scene fully connected graphs without '
                                       'self loops (what the reference dataset builds); got a different edge_index')

@@ -642,13 +642,22 @@ def _scene_par(sd, NC):
     return blk.contiguous()
 
 
+def upload(t, device):
+    """``t.to(device)`` for a small host tensor of structure data, without a host synchronisation on a ROCm device: through a pinned
+    staging copy and a non-blocking transfer on the current stream (a pageable copy blocks the host until the stream has drained)."""
+    device = torch.device(device)
+    if device.type == 'cuda' and not t.is_cuda:
+        return t.contiguous().pin_memory().to(device, non_blocking=True)
+    return t.to(device)
+
+
 def pack_scenes(ptr, NS, device):
     """ptr: (B+1,) long tensor of scene offsets -> StriveScenes (int32 device tensors)."""
     p = Packed(L.StriveScenes())
-    ptr32 = ptr.to(device=device, dtype=torch.int32).contiguous()
+    ptr32 = upload(ptr.to(torch.int32), device).contiguous()
     sizes = (ptr[1:] - ptr[:-1]).to('cpu')
     B = sizes.shape[0]
-    scene_of = torch.repeat_interleave(torch.arange(B, dtype=torch.int32), sizes).to(device).contiguous()
+    scene_of = upload(torch.repeat_interleave(torch.arange(B, dtype=torch.int32), sizes), device).contiguous()
     p.struct.NA = int(ptr[-1])
     p.struct.NS = int(NS)
     p.struct.B = int(B)
