@@ -6,15 +6,13 @@ dictionary keys and CSV files.
 
 The reference evaluates one scene at a time with shapely polygon loops per agent pair and step.  Here ``quant_eval`` puts up
 to ``batch_scenes`` consecutive scenes with the same number of steps through ONE launch of ``strive_scenario_eval_metrics``
-(strive_amd/csrc/losses.hip; one workgroup per scene, float64 on the fp32 inputs) and labels the crashes with ONE
+(strive_amd/csrc/eval_metrics.hip; one workgroup per scene, float64 on the fp32 inputs) and labels the crashes with ONE
 ``strive_kmeans_step`` against fixed centres.  The kernel returns per-scene sums and frame counts; the pooled means are
 total / count (utils/scenario_gen.py, ``PooledMetric``).
 
     python -m strive_amd.eval_adv_gen --scenarios DIR --eval_quant --cluster_path P --cluster_labels TXT --map_world synthetic --out OUT
 """
 import csv
-import glob
-import json
 import os
 
 import numpy as np
@@ -22,6 +20,8 @@ import torch
 
 from . import _lib as L
 from . import ops
+from .eval_common import LIN_MAX, lin_table, pack_env, scene_jsons
+from .eval_common import lin_table as _lin_table, pack_env as _pack_env          # noqa: F401  (the names these had while they lived here)
 from .utils.scenario_gen import log_metric_sum, log_freq_stat
 
 OUT_I = ('adv_collide', 'coll_t', 'coll_agt', 'atk_agt', 'num_coll_veh', 'num_traj_veh', 'env_coll_atk', 'env_coll_others', 'n_others',
@@ -37,7 +37,6 @@ SEQ_KEYS = ('adv_collide', 'veh_coll_rate', 'env_coll_atk', 'env_coll_others', '
             'adv_other_accel', 'adv_other_accel_fwd', 'adv_other_accel_lat', 'adv_z_ll_atk', 'adv_z_ll_other', 'match_plan_pos',
             'match_plan_ang', 'match_plan_ang_rad')                 # + sol_success, set by quant_eval: the reference's 16 keys
 MAX_OTHERS = 63
-LIN_MAX = 128                     # largest sampling grid of the drivable-area check along either axis
 RES_NAMES = ['adv_sol_success', 'sol_failed', 'adv_failed']
 STATUS_TEXT = {1: 'only the ego is in the scene', 2: 'agent offsets, attack_agt or the map index are out of range',
                3: 'more than %d non-ego agents' % MAX_OTHERS, 4: 'the drivable-area sampling grid exceeds %d samples per axis' % LIN_MAX}
@@ -48,13 +47,11 @@ def read_adv_scenes(scene_path):
     map, dt, sem, veh_att, past, fut_adv, fut_init`` and, when the file has them, ``fut_sol, fut_internal_ego, attack_t,
     attack_agt, z_adv, z_sol, z_prior_mean, z_prior_var``."""
     scenes = []
-    for path in sorted(glob.glob(os.path.join(scene_path, '*.json'))):
-        with open(path, 'r') as f:
-            jd = json.load(f)
+    for name, jd in scene_jsons(scene_path):
         if jd is None:
             print('Failed to load! Skipping')
             continue
-        sc = {'name': os.path.basename(path)[:-5], 'map': jd['map'], 'dt': jd['dt']}
+        sc = {'name': name, 'map': jd['map'], 'dt': jd['dt']}
         for key, src in (('sem', 'sem'), ('veh_att', 'lw'), ('past', 'past'), ('fut_adv', 'fut_adv'), ('fut_init', 'fut_init')):
             sc[key] = torch.tensor(jd[src])
         for key in ('fut_sol', 'fut_internal_ego'):
@@ -71,36 +68,6 @@ def read_adv_scenes(scene_path):
             sc['z_prior_var'] = torch.tensor(jd['z_prior']['var'])
         scenes.append(sc)
     return scenes
-
-
-_lin_tabs = {}
-
-
-def _lin_table(dev):
-    """fp32 ``torch.linspace(-1, 1, k)`` for k = 1..LIN_MAX one after the other (table k starts at k (k - 1) / 2), uploaded once
-    per device: the kernel picks the grid size on the device, after the collision time is known."""
-    t = _lin_tabs.get(str(dev))
-    if t is None:
-        t = torch.cat([torch.linspace(-1.0, 1.0, k) for k in range(1, LIN_MAX + 1)]).to(dev)
-        _lin_tabs[str(dev)] = t
-    return t
-
-
-class _PackEnv(object):
-    """What the map packer reads of a map environment; crop geometry the evaluation does not use gets the reference's defaults."""
-
-    def __init__(self, env):
-        self.nusc_raster, self.nusc_dx = env.nusc_raster, env.nusc_dx
-        self.bounds = list(getattr(env, 'bounds', [-17.0, -38.5, 60.0, 38.5]))
-        self.L, self.W = getattr(env, 'L', 256), getattr(env, 'W', 256)
-
-
-def _pack_env(map_env):
-    pe = map_env.__dict__.get('_strive_eval_env')
-    if pe is None or pe.nusc_raster is not map_env.nusc_raster:
-        pe = _PackEnv(map_env)
-        map_env.__dict__['_strive_eval_env'] = pe
-    return pe
 
 
 def scenario_eval_metrics(fut, ptr, lw, atk_agt, dt, z=None, mu=None, var=None, plan_fit=None, has_fit=None, map_env=None, mapix=None,
@@ -145,8 +112,8 @@ def scenario_eval_metrics(fut, ptr, lw, atk_agt, dt, z=None, mu=None, var=None, 
         return out_i, out_d, status
     map_ref, lin, mapix_t = None, None, None
     if map_env is not None:
-        map_ref = ops._map_pack(_pack_env(map_env), dev).ref()
-        lin = _lin_table(dev)
+        map_ref = ops._map_pack(pack_env(map_env), dev).ref()
+        lin = lin_table(dev)
         mapix_t = i32(mapix, 0)
     lib.call('strive_scenario_eval_metrics', L.ptr(fut), L.ptr(ptr), L.ptr(lw), L.ptr(atk_agt), L.ptr(dt), L.ptr(z), L.ptr(mu), L.ptr(var),
              Dz, L.ptr(plan_fit), L.ptr(has_fit), map_ref, L.ptr(mapix_t), L.ptr(lin), LIN_MAX, L.ptr(want_feat), B, NA, T,

@@ -5,7 +5,7 @@ scenarios and, as the control, for regular scenes -- same function names, signat
 The reference evaluates one scene at a time: ``planner.reset(..., 1, ...)``, a numpy planner rollout, then one shapely polygon
 per agent and up-sampled step.  Here ``run_planner_eval`` collects up to ``batch_scenes`` scenes into ONE ``planner.reset`` /
 ``planner.rollout`` (``strive_planner_rollout``) and ONE metrics launch (``strive_planner_eval_metrics``,
-strive_amd/csrc/losses.hip: up-sampling, box IoU of the ego against every agent and fine step, first hit, collision index,
+strive_amd/csrc/eval_metrics.hip: up-sampling, box IoU of the ego against every agent and fine step, first hit, collision index,
 impact speed and the acceleration series, float64).  The kernel returns per-scene sums and frame counts; the pooled means the
 reference prints (``np.mean`` over the frames of all scenes) are total / count (utils/scenario_gen.py, ``PooledMetric``).
 
@@ -14,7 +14,6 @@ Command line (the nuScenes devkit and data are not needed for scenario directori
     python -m strive_amd.eval_planner --scenario_dir DIR --skip_regular --lane_world synthetic --out OUT
 """
 import csv
-import glob
 import json
 import os
 
@@ -23,6 +22,7 @@ import torch
 
 from . import _lib as L
 from . import ops
+from .eval_common import scene_jsons
 from .utils.scenario_gen import log_metric_sum, log_freq_stat, print_metrics
 
 INTERP_SCALE = 3                 # the reference up-samples x3 before checking collisions (src/eval_planner.py:129)
@@ -37,14 +37,12 @@ def read_adv_scenes(scene_path):
     :90-112): ``name, map, attack_t, past, init_state`` (last past step), ``veh_att``, ``adv_fut`` (agents 1..) and ``plan_fut``
     (agent 0 of ``fut_adv``)."""
     scenes = []
-    for path in sorted(glob.glob(os.path.join(scene_path, '*.json'))):
-        with open(path, 'r') as f:
-            jd = json.load(f)
+    for name, jd in scene_jsons(scene_path):
         if jd is None:
             continue
         fut = torch.tensor(jd['fut_adv'])
         past = torch.tensor(jd['past'])
-        scenes.append({'name': os.path.basename(path)[:-5], 'map': jd['map'], 'attack_t': jd.get('attack_t'), 'past': past,
+        scenes.append({'name': name, 'map': jd['map'], 'attack_t': jd.get('attack_t'), 'past': past,
                        'init_state': past[:, -1, :], 'veh_att': torch.tensor(jd['lw']), 'adv_fut': fut[1:], 'plan_fut': fut[0]})
     return scenes
 

@@ -27,7 +27,7 @@ import torch
 
 from . import _lib as L
 from . import ops
-from .eval_adv_gen import LIN_MAX, _lin_table, _pack_env
+from .eval_common import LIN_MAX, lin_table, pack_env
 from .losses.common import log_normal
 
 G_ERR, G_DISP, G_VEH, G_ENV, G_GRID_GIVEN = 1, 2, 4, 8, 16
@@ -98,8 +98,8 @@ def traffic_eval_metrics(pred, ptr, lw, state_normalizer, att_normalizer, gt=Non
             groups |= G_GRID_GIVEN
             for i, v in enumerate((int(grid[0]), int(grid[1]), 1)):          # (fills are launches: no staging copy, no synchronisation)
                 out['grid_i'][i:i + 1].fill_(v)
-        map_ref = ops._map_pack(_pack_env(map_env), dev).ref()
-        lin = _lin_table(dev)
+        map_ref = ops._map_pack(pack_env(map_env), dev).ref()
+        lin = lin_table(dev)
         mapix_t = torch.as_tensor(mapix).to(device=dev, dtype=torch.int32).reshape(B).contiguous()
     new('status', (B,), torch.int32, 0)
     if B == 0 or groups == 0:

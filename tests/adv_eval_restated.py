@@ -1,4 +1,4 @@
-"""float64 numpy restatement of strive_scenario_eval_metrics and strive_kmeans_step (strive_amd/csrc/losses.hip), formula by formula
+"""float64 numpy restatement of strive_scenario_eval_metrics and strive_kmeans_step (strive_amd/csrc/eval_metrics.hip), formula by formula
 (reference src/eval_adv_gen.py:116-168, 323-513; src/losses/adv_gen_nusc.py:517-644; src/losses/traffic_model.py:421-463;
 src/datasets/nuscenes_utils.py:205-298, 416-428; src/losses/common.py:26-42; src/utils/transforms.py:78-139).  Test infrastructure only;
 nothing here is loaded by the product."""

@@ -1,5 +1,5 @@
 """Batched scenario evaluation and collision clustering (strive_amd/eval_adv_gen.py, strive_amd/cluster_scenarios.py ->
-strive_scenario_eval_metrics, strive_kmeans_step, strive_amd/csrc/losses.hip) against the reference's src/eval_adv_gen.py and
+strive_scenario_eval_metrics, strive_kmeans_step, strive_amd/csrc/eval_metrics.hip) against the reference's src/eval_adv_gen.py and
 src/cluster_scenarios.py (fixture g18, tests/golden/make_golden_adv_eval.py) and against a float64 numpy restatement
 (tests/adv_eval_restated.py).
 

@@ -1,4 +1,4 @@
-"""Batched planner evaluation (strive_amd/eval_planner.py -> strive_planner_eval_metrics, strive_amd/csrc/losses.hip) against the
+"""Batched planner evaluation (strive_amd/eval_planner.py -> strive_planner_eval_metrics, strive_amd/csrc/eval_metrics.hip) against the
 reference's src/eval_planner.py (fixture g17, tests/golden/make_golden_planner_eval.py) and against a float64 numpy restatement.
 
 Tolerances (derived, not fitted).  Coordinates are metres on the 256 m synthetic world, dt = 0.5 s.

@@ -1,4 +1,4 @@
-"""Batched model evaluation (strive_amd/test_traffic.py -> strive_traffic_eval_metrics, strive_amd/csrc/losses.hip; checkpoints through
+"""Batched model evaluation (strive_amd/test_traffic.py -> strive_traffic_eval_metrics, strive_amd/csrc/eval_metrics.hip; checkpoints through
 strive_amd/utils/torch.py) against the reference's src/test_traffic.py and the metric functions of src/losses/traffic_model.py.
 
 Fixture g19_traffic_eval.npz (tests/golden/make_golden_traffic_eval.py, README_g19.md): ``inj/*`` the reference's compute_err,

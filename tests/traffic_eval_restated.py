@@ -1,4 +1,4 @@
-"""float64 numpy restatement of strive_traffic_eval_metrics (strive_amd/csrc/losses.hip), formula by formula and in the kernel's order
+"""float64 numpy restatement of strive_traffic_eval_metrics (strive_amd/csrc/eval_metrics.hip), formula by formula and in the kernel's order
 of summation (reference src/losses/traffic_model.py:120-164, 297-364, 366-419, 465-545; src/datasets/nuscenes_utils.py:266-298,
 416-428; src/datasets/utils.py:75-90).  Test infrastructure only; nothing here is loaded by the product."""
 import numpy as np
