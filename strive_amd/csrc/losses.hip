@@ -6,6 +6,7 @@
 // blocks exist: sum_b n_b^2 slots per time sample instead of NA^2 (32x fewer at 32 scenes of 16).
 // One thread owns (agent i, time t) and walks the members j of i's scene; the scene's circle centres
 // are a few hundred bytes, so everything stays in registers / L1.
+#include <type_traits>
 #include "common.h"
 
 #define NCIRC 5
@@ -110,12 +111,28 @@ __global__ __launch_bounds__(256) void veh_coll_fwd_kernel(VehArgs a, float* __r
     }
 }
 
+// The float64 sums[] a fused loss call (AvoidCollLoss, AdvGenLoss: below) leaves in its workspace for its backward kernels.
+// AvoidCollLoss has the first AV_TERMS; AdvGenLoss adds the planner pairs, which like them are summed over workgroup partials
+// (ADV_TERMS accumulators), and two counts that its final kernel forms itself (ADV_SUMS entries).
+enum LossSum {
+    S_VEH, S_VEH_N,             // vehicle penalties: sum, number of colliding valid slots
+    S_ENV, S_ENV_N,             // environment penalties: sum, number of rows with a collision point
+    S_PRIOR, S_INIT,            // prior NLL sum, init-z sum (AdvGenLoss: re-weighted per row)
+    AV_TERMS,
+    S_PLAN = AV_TERMS, S_PLAN_N,    // planner-involving slots: re-weighted sum, count
+    ADV_TERMS,
+    S_ROWS = ADV_TERMS, S_SCENES,   // latent rows / scenes that are alive (all of them without a mask)
+    ADV_SUMS,
+    S_CRASH = ADV_SUMS,             // sum of the scenes' crash terms: stays inside adv_final_kernel (ADV_LOCAL values there)
+    ADV_LOCAL
+};
+
 // Gradient of the masked MEAN of the penalties without a d_pen tensor (fused AvoidCollLoss): d_pen(slot) = g for the
 // slots that are colliding and valid, g = d_loss * w / max(#such slots, 1) read from the forward's sums.
 struct VehImplicit {
     const uint8_t* hit;       // (T,P)
     const uint8_t* valid;     // (P)
-    const double* sums;       // [1] = number of colliding valid slots ([7] = of planner slots, see slot_ne)
+    const double* sums;       // LossSum: S_VEH_N = number of colliding valid slots (S_PLAN_N = of planner slots, see slot_ne)
     const float* d_loss;      // device scalar
     float w;
     // AdvGenLoss: slots that involve the scene's ego form a second masked mean, weighted per slot by rew of the non-ego
@@ -144,10 +161,10 @@ __global__ __launch_bounds__(256) void veh_coll_bwd_kernel(VehArgs a, const floa
     float g[4] = {0.f, 0.f, 0.f, 0.f};
     float gs = 0.f, gs2 = 0.f;
     if (IMPL) {
-        const double c = im.sums[1];
+        const double c = im.sums[S_VEH_N];
         gs = (float)((double)im.d_loss[0] * (double)im.w / (c < 1.0 ? 1.0 : c));
         if (im.slot_ne) {
-            const double c2 = im.sums[7];
+            const double c2 = im.sums[S_PLAN_N];
             gs2 = (float)((double)im.d_loss[0] * (double)im.w2 / (c2 < 1.0 ? 1.0 : c2));
         }
     }
@@ -341,11 +358,22 @@ extern "C" int strive_interp_traj_bwd(const float* in, const float* d_out, int32
 }
 
 // =============================================================================================
-// AvoidCollLoss in one call per direction (reference src/losses/adv_gen_nusc.py:264-341).
-//   forward : interp_traj_fwd -> veh_coll_fwd -> coll_point (rows) -> avoid_partial -> avoid_final     (5 launches)
-//   backward: avoid_grad (environment term, d_z) -> veh_coll_bwd<implicit> -> interp_traj_bwd            (3 launches)
-// against ~60 + ~45 elementwise torch operators.  All sums are float64 partials per workgroup added in a fixed order
-// (deterministic); the means divide by max(count, 1) like the reference's "[0.] when nothing collides" sentinel does.
+// AvoidCollLoss (reference src/losses/adv_gen_nusc.py:264-341) and AdvGenLoss (:53-262) in one call per direction.
+//   AvoidCollLoss forward : interp_traj_fwd -> veh_coll_fwd -> coll_point (rows) -> loss_partial<false> -> avoid_final  (5 launches)
+//                 backward: loss_grad<false> (environment term, d_z) -> veh_coll_bwd<implicit> -> interp_traj_bwd            (3 launches)
+//   AdvGenLoss    forward : interp -> veh_coll_fwd -> coll_point (non-ego rows) -> adv_crash (one workgroup per scene: distances to
+//                           the target, behind test, per-scene soft-min, crash term, prior re-weights) -> loss_partial<true> ->
+//                           adv_final                                                                                   (6 launches)
+//                 backward: loss_grad<true> (environment term, d_z) -> veh_coll_bwd<implicit, per-slot weights> -> interp_bwd -> adv_crash_bwd
+// against ~60 + ~45 (AvoidCollLoss) and ~140 + ~110 (AdvGenLoss) elementwise / scatter torch operators.  All sums are float64
+// partials per workgroup added in a fixed order (deterministic); the means divide by max(count, 1) like the reference's "[0.]
+// when nothing collides" sentinel does.  AdvGenLoss is AvoidCollLoss plus the planner pairs, the per-row re-weights and the
+// crash term, and is written that way: AdvArgs / AdvWs embed AvoidArgs / AvoidWs, the partial-sum and gradient kernels are
+// templates over the objective (the AvoidCollLoss forms compile none of AdvGenLoss's loads), and the
+// two host sequences share their stages.
+// The "every attacker is always behind its target" escape (:120-123) is a property of the whole batch: adv_crash evaluates the
+// soft-min with and without the behind mask and leaves a per-scene flag; the kernels after it form the batch-wide AND themselves
+// and pick the variant.
 // =============================================================================================
 extern "C" int strive_coll_point_rows(const StriveMap* map, const float* fine, int32_t TO, const int32_t* agent_of,
                                       const float* lw, const int32_t* mapix, int32_t NE, int32_t gl, int32_t gw,
@@ -354,7 +382,11 @@ extern "C" int strive_coll_point_rows(const StriveMap* map, const float* fine, i
 
 #define AV_BLOCKS 1024
 #define NT_AV 256
-#define AV_TERMS 6          // veh sum, veh count, env sum, env count, prior NLL sum, init-z sum
+#define ADV_MAXE 1024       // (non-ego agents of a scene) x (crash time samples) the crash kernel keeps in LDS
+
+// out[] of the two forward calls (ABI, include/strive_hip.h): the named slots, zeros from *_END up to *_SIZE
+enum AvoidOut { AO_LOSS, AO_VEH, AO_ENV, AO_PRIOR, AO_INIT, AO_VEH_N, AO_ENV_N, AO_END, AO_SIZE = 8 };
+enum AdvOut { DO_LOSS, DO_VEH, DO_PLAN, DO_ENV, DO_PRIOR, DO_INIT, DO_CRASH, DO_VEH_N, DO_PLAN_N, DO_ENV_N, DO_SEL, DO_END, DO_SIZE = 16 };
 
 struct AvoidWs {
     float* fine;            // (NA,TO,4)
@@ -368,17 +400,21 @@ struct AvoidWs {
     float* d_fine;          // (NA,TO,4) backward scratch
 };
 
-static size_t avoid_ws_bytes(size_t NA, size_t TO, size_t P, size_t NE) {
-    size_t b = 0;
-    b += strive_align_up(NA * TO * 16, 256) * 2;
-    b += strive_align_up(TO * P * 4, 256) + 2 * strive_align_up(TO * P, 256);
-    b += strive_align_up(NE * TO * 8, 256) + strive_align_up(NE * TO * 4, 256);
-    b += strive_align_up((size_t)AV_BLOCKS * AV_TERMS * 8, 256) + 256;
-    return b + 256;
-}
+struct AdvWs {
+    AvoidWs av;
+    double* partial;        // (AV_BLOCKS, ADV_TERMS)
+    double* sums;           // (ADV_SUMS)
+    float* soft2;           // (2, NE, NT)   variant 0 = with the behind mask, 1 = without
+    float* rew2;            // (2, NE)
+    float* crash2;          // (2, B)
+    int32_t* scene_flag;    // (B) 1 = every non-ego agent of the scene is always behind
+    int32_t* sel;           // (1) chosen variant
+    float* rew_sel;         // (NE) re-weights of the chosen variant (the backward kernels read these)
+};
 
-static AvoidWs avoid_carve(void* p, size_t bytes, size_t NA, size_t TO, size_t P, size_t NE) {
-    StriveArena ar(p, bytes);
+// Each workspace is laid out by ONE function, which carves it from the caller's buffer and -- over a null base of unlimited
+// capacity, where the arena's offset is the size -- measures it; both end in 256 bytes of slack.
+static AvoidWs avoid_layout(StriveArena& ar, size_t NA, size_t TO, size_t P, size_t NE) {
     AvoidWs w;
     w.fine = ar.take<float>(NA * TO * 4);
     w.d_fine = ar.take<float>(NA * TO * 4);
@@ -389,7 +425,35 @@ static AvoidWs avoid_carve(void* p, size_t bytes, size_t NA, size_t TO, size_t P
     w.cnt = ar.take<int32_t>(NE * TO);
     w.partial = ar.take<double>((size_t)AV_BLOCKS * AV_TERMS);
     w.sums = ar.take<double>(AV_TERMS);
+    ar.take<char>(256);
     return w;
+}
+
+static AdvWs adv_layout(StriveArena& ar, size_t NA, size_t TO, size_t P, size_t NE, size_t NT, size_t B) {
+    AdvWs w;
+    w.av = avoid_layout(ar, NA, TO, P, NE);
+    w.partial = ar.take<double>((size_t)AV_BLOCKS * ADV_TERMS);
+    w.sums = ar.take<double>(ADV_SUMS);
+    w.soft2 = ar.take<float>(2 * NE * NT);
+    w.rew2 = ar.take<float>(2 * NE);
+    w.crash2 = ar.take<float>(2 * B);
+    w.scene_flag = ar.take<int32_t>(B);
+    w.sel = ar.take<int32_t>(1);
+    w.rew_sel = ar.take<float>(NE);
+    ar.take<char>(256);
+    return w;
+}
+
+static size_t avoid_ws_bytes(size_t NA, size_t TO, size_t P, size_t NE) {
+    StriveArena ar(nullptr, SIZE_MAX);
+    avoid_layout(ar, NA, TO, P, NE);
+    return ar.off;
+}
+
+static size_t adv_ws_bytes(size_t NA, size_t TO, size_t P, size_t NE, size_t NT, size_t B) {
+    StriveArena ar(nullptr, SIZE_MAX);
+    adv_layout(ar, NA, TO, P, NE, NT, B);
+    return ar.off;
 }
 
 struct AvoidArgs {
@@ -407,289 +471,6 @@ struct AvoidArgs {
     const uint8_t* scene_alive;     // (B) or null; AdvGenLoss only (a quarantined scene's rows count as "no collision point")
     const int32_t* scene_of;        // (NA)
 };
-
-// off-road penalty of row (e, t): 1 - |c - p| / r for rows with a collision point (reference :384-403)
-__device__ __forceinline__ bool env_row(const AvoidArgs& a, int row, float& dx, float& dy, float& d, float& pd) {
-    const float px = a.pt[(size_t)row * 2], py = a.pt[(size_t)row * 2 + 1];
-    if (!(px + py == px + py)) return false;      // NaN point = no collision point
-    const int e = row / a.TO, t = row - e * a.TO;
-    if (a.scene_alive && !a.scene_alive[a.scene_of[a.env_agent[e]]]) return false;
-    const float* c = a.fine + ((size_t)a.env_agent[e] * a.TO + t) * 4;
-    dx = c[0] - px;
-    dy = c[1] - py;
-    d = sqrtf(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)));
-    pd = a.pdist[e];
-    return true;
-}
-
-__global__ __launch_bounds__(256) void avoid_partial_kernel(AvoidArgs a, double* __restrict__ partial) {
-    __shared__ double s_red[4][AV_TERMS];
-    const int tid = threadIdx.x;
-    const long long stride = (long long)gridDim.x * blockDim.x;
-    const long long g0 = (long long)blockIdx.x * blockDim.x + tid;
-    double acc[AV_TERMS] = {0, 0, 0, 0, 0, 0};
-    if (a.w_veh > 0.f) {
-        // (t, slot) walked with 32-bit indices: slot fastest, so pen / hit reads are contiguous and `valid` stays in L1
-        const int per_t = (a.P + NT_AV - 1) / NT_AV;                 // slot chunks of one time sample
-        const long long nchunk = (long long)a.TO * per_t;
-        for (long long ch = blockIdx.x; ch < nchunk; ch += gridDim.x) {
-            const int t = (int)(ch / per_t), slot = (int)(ch - (long long)t * per_t) * NT_AV + tid;
-            if (slot < a.P) {
-                const size_t i = (size_t)t * a.P + slot;
-                if (a.hit[i] && a.valid[slot]) { acc[0] += (double)a.pen[i]; acc[1] += 1.0; }
-            }
-        }
-    }
-    if (a.w_env > 0.f) {
-        const long long n = (long long)a.NE * a.TO;
-        for (long long i = g0; i < n; i += stride) {
-            float dx, dy, d, pd;
-            if (env_row(a, (int)i, dx, dy, d, pd)) { acc[2] += (double)(1.0f - d / pd); acc[3] += 1.0; }
-        }
-    }
-    if (a.w_prior > 0.f || a.w_init > 0.f) {
-        const long long n = (long long)a.NZ * a.D;
-        for (long long i = g0; i < n; i += stride) {
-            const float z = a.z[i];
-            if (a.w_prior > 0.f) {
-                // -log N(z; mu, var) per element as losses/common.py:26-41 evaluates it in fp32
-                const float m = a.mu[i], v = a.var[i];
-                const float dz = z - m;
-                const float lp = -logf(sqrtf(v)) - 0.91893853320467267f - (dz * dz) / (2.0f * v);
-                acc[4] -= (double)lp;
-            }
-            if (a.w_init > 0.f) {
-                const float di = a.init_z[i] - z;
-                acc[5] += (double)(di * di);
-            }
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < AV_TERMS; ++k) acc[k] = wave_sum_d(acc[k]);
-    if ((tid & 63) == 0)
-        for (int k = 0; k < AV_TERMS; ++k) s_red[tid >> 6][k] = acc[k];
-    __syncthreads();
-    if (tid < AV_TERMS) partial[(size_t)blockIdx.x * AV_TERMS + tid] = s_red[0][tid] + s_red[1][tid] + s_red[2][tid] + s_red[3][tid];
-}
-
-__global__ __launch_bounds__(64) void avoid_final_kernel(AvoidArgs a, const double* __restrict__ partial, int nblocks,
-                                                           double* __restrict__ sums, float* __restrict__ out) {
-    __shared__ double s[AV_TERMS];
-    const int tid = threadIdx.x;
-    // lanes stride over the workgroup partials, then a shuffle tree: a fixed order (deterministic), 16 steps instead of 1024
-    for (int k = 0; k < AV_TERMS; ++k) {
-        double v = 0.0;
-        for (int b = tid; b < nblocks; b += 64) v += partial[(size_t)b * AV_TERMS + k];
-        v = wave_sum_d(v);
-        if (tid == 0) { s[k] = v; sums[k] = v; }
-    }
-    __syncthreads();
-    if (tid == 0) {
-        const double veh = s[0] / (s[1] < 1.0 ? 1.0 : s[1]);
-        const double env = s[2] / (s[3] < 1.0 ? 1.0 : s[3]);
-        const double pri = a.prior_den > 0.f ? s[4] / (double)a.prior_den : 0.0;
-        const double ini = a.init_den > 0.f ? s[5] / (double)a.init_den : 0.0;
-        double loss = 0.0;
-        if (a.w_veh > 0.f) loss += (double)a.w_veh * veh;
-        if (a.w_env > 0.f) loss += (double)a.w_env * env;
-        if (a.w_prior > 0.f) loss += (double)a.w_prior * pri;
-        if (a.w_init > 0.f) loss += (double)a.w_init * ini;
-        out[0] = (float)loss;
-        out[1] = (float)veh;
-        out[2] = (float)env;
-        out[3] = (float)pri;
-        out[4] = (float)ini;
-        out[5] = (float)s[1];
-        out[6] = (float)s[3];
-        out[7] = 0.f;
-    }
-}
-
-// d_fine of the environment term -- every (agent, t) row is written, zeros where the agent takes no environment term or
-// has no collision point, so the vehicle term can accumulate on top without a memset -- and d_z
-__global__ __launch_bounds__(256) void avoid_grad_kernel(AvoidArgs a, const int32_t* __restrict__ env_of_agent,
-                                                           const double* __restrict__ sums, const float* __restrict__ d_loss,
-                                                           float* __restrict__ d_fine, float* __restrict__ d_z) {
-    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    const long long n_rows = (long long)a.NA * a.TO;
-    const float gl = d_loss[0];
-    if (idx < n_rows) {
-        const int ag = (int)(idx / a.TO), t = (int)(idx - (long long)ag * a.TO);
-        float gx = 0.f, gy = 0.f;
-        const int e = (a.w_env > 0.f && env_of_agent) ? env_of_agent[ag] : -1;
-        if (e >= 0) {
-            float dx, dy, d, pd;
-            if (env_row(a, e * a.TO + t, dx, dy, d, pd) && d > 0.f) {
-                const double c = sums[3];
-                const float gs = (float)((double)gl * (double)a.w_env / (c < 1.0 ? 1.0 : c));
-                const float k = -gs / (d * pd);      // pen = 1 - d / pd  ->  d pen / d c = -(c - p) / (d * pd)
-                gx = k * dx;
-                gy = k * dy;
-            }
-        }
-        float* o = d_fine + (size_t)idx * 4;
-        o[0] = gx; o[1] = gy; o[2] = 0.f; o[3] = 0.f;
-        return;
-    }
-    const long long i = idx - n_rows;
-    if (i < (long long)a.NZ * a.D) {
-        const float z = a.z[i];
-        float g = 0.f;
-        if (a.w_prior > 0.f) g += gl * a.w_prior / a.prior_den * ((z - a.mu[i]) / a.var[i]);
-        if (a.w_init > 0.f) g += gl * a.w_init / a.init_den * (2.0f * (z - a.init_z[i]));
-        d_z[i] = g;
-    }
-}
-
-static AvoidArgs avoid_args(const StriveScenes* sc, const StriveAvoidColl* h, const AvoidWs& w, int TO, const float* z,
-                            const float* mu, const float* var) {
-    AvoidArgs a;
-    a.NA = sc->NA; a.TO = TO; a.P = h->P; a.NE = h->NE; a.NZ = h->NZ; a.D = h->D;
-    a.prior_den = h->prior_den; a.init_den = h->init_den;
-    a.fine = w.fine; a.pen = w.pen; a.hit = w.hit; a.valid = h->pair_valid;
-    a.env_agent = h->env_agent; a.pt = w.pt; a.pdist = h->env_pdist;
-    a.z = z; a.mu = mu; a.var = var; a.init_z = h->init_z;
-    a.w_veh = h->w_veh; a.w_env = h->w_env; a.w_prior = h->w_prior; a.w_init = h->w_init;
-    a.scene_alive = nullptr; a.scene_of = sc->scene_of;
-    return a;
-}
-
-static int avoid_check(const StriveScenes* sc, const StriveAvoidColl* h, int T) {
-    STRIVE_CHECK_ARG(sc && h, "null argument");
-    STRIVE_CHECK_ARG(sc->NS == 1, "collision losses take one trajectory per agent");
-    STRIVE_CHECK_ARG(T > 0 && h->scale >= 1 && h->P >= 0 && h->NE >= 0 && h->NZ >= 0 && h->D >= 0, "bad sizes");
-    STRIVE_CHECK_ARG(h->i0 && h->i1 && h->w0 && h->w1, "null interpolation taps");
-    if (h->w_veh > 0.f) STRIVE_CHECK_ARG(h->pair_off && h->cent_x && h->rad && h->pair_valid, "null vehicle-term constants");
-    if (h->w_env > 0.f && h->NE > 0)
-        STRIVE_CHECK_ARG(h->env_agent && h->env_of_agent && h->env_lw && h->env_mapix && h->env_pdist && h->lin_l && h->lin_w &&
-                             h->gl > 0 && h->gw > 0,
-                         "null environment-term constants");
-    if (h->w_init > 0.f) STRIVE_CHECK_ARG(h->init_z, "null init_z");
-    return 0;
-}
-
-extern "C" size_t strive_avoid_coll_workspace_bytes(const StriveScenes* sc, const StriveAvoidColl* h, int32_t T) {
-    if (!sc || !h || T <= 0 || h->scale < 1) return 0;
-    return avoid_ws_bytes((size_t)sc->NA, (size_t)T * h->scale, (size_t)h->P, (size_t)h->NE);
-}
-
-extern "C" int strive_avoid_coll_fwd(const StriveScenes* sc, const StriveMap* map, const StriveAvoidColl* h, const float* traj,
-                                     int32_t T, const float* z, const float* mu, const float* var, float* out, void* ws,
-                                     size_t ws_bytes, strive_stream_t stream) {
-    if (int rc = avoid_check(sc, h, T)) return rc;
-    STRIVE_CHECK_ARG(traj && out && ws, "null argument");
-    if (h->w_prior > 0.f) STRIVE_CHECK_ARG(z && mu && var, "null latent tensors");
-    if (h->w_init > 0.f) STRIVE_CHECK_ARG(z, "null latent tensors");
-    if (h->w_env > 0.f && h->NE > 0) STRIVE_CHECK_ARG(map, "null map");
-    const int NA = sc->NA, TO = T * h->scale;
-    STRIVE_CHECK_ARG(ws_bytes >= avoid_ws_bytes(NA, TO, h->P, h->NE), "workspace too small");
-    AvoidWs w = avoid_carve(ws, ws_bytes, NA, TO, h->P, h->NE);
-    hipStream_t st = (hipStream_t)stream;
-    if (NA > 0) {
-        if (int rc = strive_interp_traj_fwd(traj, NA, T, TO, h->i0, h->i1, h->w0, h->w1, w.fine, stream)) return rc;
-        if (h->w_veh > 0.f && h->P > 0)
-            if (int rc = veh_coll_fwd_masked(sc, h->pair_off, h->P, w.fine, TO, h->cent_x, h->rad, h->buffer, nullptr, w.pen, w.hit, w.amin,
-                                             stream, /*cull=*/1))
-                return rc;
-        if (h->w_env > 0.f && h->NE > 0)
-            if (int rc = strive_coll_point_rows(map, w.fine, TO, h->env_agent, h->env_lw, h->env_mapix, h->NE, h->gl, h->gw,
-                                                h->lin_l, h->lin_w, w.pt, w.cnt, stream))
-                return rc;
-    }
-    AvoidArgs a = avoid_args(sc, h, w, TO, z, mu, var);
-    if (h->P == 0) a.w_veh = 0.f;          // nothing to sum; the weight is re-applied below (mean of nothing = 0)
-    if (h->NE == 0) a.w_env = 0.f;
-    long long work = (long long)TO * h->P;
-    if ((long long)h->NE * TO > work) work = (long long)h->NE * TO;
-    if ((long long)h->NZ * h->D > work) work = (long long)h->NZ * h->D;
-    int nb = (int)((work + 2047) / 2048);
-    nb = nb < 1 ? 1 : (nb > AV_BLOCKS ? AV_BLOCKS : nb);
-    hipLaunchKernelGGL(avoid_partial_kernel, dim3(nb), dim3(256), 0, st, a, w.partial);
-    STRIVE_CHECK_LAUNCH();
-    hipLaunchKernelGGL(avoid_final_kernel, dim3(1), dim3(64), 0, st, a, (const double*)w.partial, nb, w.sums, out);
-    STRIVE_CHECK_LAUNCH();
-    return 0;
-}
-
-extern "C" int strive_avoid_coll_bwd(const StriveScenes* sc, const StriveAvoidColl* h, const float* traj, int32_t T,
-                                     const float* z, const float* mu, const float* var, const float* d_loss, void* ws,
-                                     size_t ws_bytes, float* d_traj, float* d_z, strive_stream_t stream) {
-    if (int rc = avoid_check(sc, h, T)) return rc;
-    STRIVE_CHECK_ARG(traj && d_loss && ws && d_traj, "null argument");
-    const int NA = sc->NA, TO = T * h->scale;
-    STRIVE_CHECK_ARG(ws_bytes >= avoid_ws_bytes(NA, TO, h->P, h->NE), "workspace too small");
-    if (NA == 0) return 0;
-    AvoidWs w = avoid_carve(ws, ws_bytes, NA, TO, h->P, h->NE);
-    hipStream_t st = (hipStream_t)stream;
-    AvoidArgs a = avoid_args(sc, h, w, TO, z, mu, var);
-    if (h->NE == 0) a.w_env = 0.f;
-    const bool latent = (h->w_prior > 0.f || h->w_init > 0.f) && h->D > 0;
-    if (latent) STRIVE_CHECK_ARG(z && d_z && (h->w_prior <= 0.f || (mu && var)), "null latent tensors");
-    if (!latent) a.D = 0;
-    const long long n = (long long)NA * TO + (long long)a.NZ * a.D;
-    hipLaunchKernelGGL(avoid_grad_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a, h->env_of_agent,
-                       (const double*)w.sums, d_loss, w.d_fine, d_z);
-    STRIVE_CHECK_LAUNCH();
-    if (h->w_veh > 0.f && h->P > 0) {
-        VehImplicit im;
-        im.hit = w.hit; im.valid = h->pair_valid; im.sums = w.sums; im.d_loss = d_loss; im.w = h->w_veh;
-        im.slot_ne = nullptr; im.rew = nullptr; im.w2 = 0.f;
-        const long long nv = (long long)NA * TO * VG;
-        hipLaunchKernelGGL(veh_coll_bwd_kernel<true>, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, st,
-                           veh_args(sc, h->pair_off, h->P, w.fine, TO, h->cent_x, h->rad, h->buffer), (const float*)nullptr,
-                           (const uint8_t*)w.amin, w.d_fine, im);
-        STRIVE_CHECK_LAUNCH();
-    }
-    return strive_interp_traj_bwd(traj, w.d_fine, NA, T, TO, h->scale, h->i0, h->i1, h->w0, h->w1, d_traj, stream);
-}
-
-
-// =============================================================================================
-// AdvGenLoss in one call per direction (reference src/losses/adv_gen_nusc.py:53-262).
-//   forward : interp -> veh_coll_fwd -> coll_point (non-ego rows) -> adv_crash (one workgroup per scene: distances to the
-//             target, behind test, per-scene soft-min, crash term, prior re-weights) -> adv_partial -> adv_final   (6 launches)
-//   backward: adv_grad (environment term, d_z) -> veh_coll_bwd<implicit, per-slot weights> -> interp_bwd -> adv_crash_bwd
-// against ~140 + ~110 elementwise / scatter torch operators.  The "every attacker is always behind its target" escape
-// (:120-123) is a property of the whole batch: adv_crash evaluates the soft-min with and without the behind mask and leaves a
-// per-scene flag; the kernels after it form the batch-wide AND themselves and pick the variant.
-// =============================================================================================
-#define ADV_TERMS 8         // veh sum, veh count, env sum, env count, weighted prior sum, weighted init sum, planner sum, planner count
-#define ADV_SUMS 10         // sums[]: the terms above, then [8] latent rows and [9] scenes that are alive (all of them without a mask)
-#define ADV_MAXE 1024       // (non-ego agents of a scene) x (crash time samples) the crash kernel keeps in LDS
-
-struct AdvWs {
-    AvoidWs av;
-    double* partial;        // (AV_BLOCKS, ADV_TERMS)
-    double* sums;           // (ADV_TERMS)
-    float* soft2;           // (2, NE, NT)   variant 0 = with the behind mask, 1 = without
-    float* rew2;            // (2, NE)
-    float* crash2;          // (2, B)
-    int32_t* scene_flag;    // (B) 1 = every non-ego agent of the scene is always behind
-    int32_t* sel;           // (1) chosen variant
-    float* rew_sel;         // (NE) re-weights of the chosen variant (the backward kernels read these)
-};
-
-static size_t adv_ws_bytes(size_t NA, size_t TO, size_t P, size_t NE, size_t NT, size_t B) {
-    return avoid_ws_bytes(NA, TO, P, NE) + strive_align_up((size_t)AV_BLOCKS * ADV_TERMS * 8, 256) + 256 +
-           strive_align_up(2 * NE * NT * 4, 256) + strive_align_up(2 * NE * 4, 256) + strive_align_up(2 * B * 4, 256) +
-           strive_align_up(B * 4, 256) + strive_align_up(NE * 4, 256) + 256 + 256;
-}
-
-static AdvWs adv_carve(void* p, size_t bytes, size_t NA, size_t TO, size_t P, size_t NE, size_t NT, size_t B) {
-    const size_t ab = avoid_ws_bytes(NA, TO, P, NE);
-    AdvWs w;
-    w.av = avoid_carve(p, ab, NA, TO, P, NE);
-    StriveArena ar((char*)p + ab, bytes - ab);
-    w.partial = ar.take<double>((size_t)AV_BLOCKS * ADV_TERMS);
-    w.sums = ar.take<double>(ADV_SUMS);
-    w.soft2 = ar.take<float>(2 * NE * NT);
-    w.rew2 = ar.take<float>(2 * NE);
-    w.crash2 = ar.take<float>(2 * B);
-    w.scene_flag = ar.take<int32_t>(B);
-    w.sel = ar.take<int32_t>(1);
-    w.rew_sel = ar.take<float>(NE);
-    return w;
-}
 
 struct AdvArgs {
     AvoidArgs a;
@@ -710,13 +491,49 @@ struct AdvArgs {
     float* rew_sel;
 };
 
-// block-wide reductions of a 256-thread workgroup in a fixed order (wave tree, then waves 0..3)
+// what a kernel written for both objectives takes, and the AvoidCollLoss part of it
+template <bool ADV> using LossArgs = typename std::conditional<ADV, AdvArgs, AvoidArgs>::type;
+__device__ __forceinline__ const AvoidArgs& avoid_part(const AvoidArgs& a) { return a; }
+__device__ __forceinline__ const AvoidArgs& avoid_part(const AdvArgs& A) { return A.a; }
+
+// off-road penalty of row (e, t): 1 - |c - p| / r for rows with a collision point (reference :384-403)
+__device__ __forceinline__ bool env_row(const AvoidArgs& a, int row, float& dx, float& dy, float& d, float& pd) {
+    const float px = a.pt[(size_t)row * 2], py = a.pt[(size_t)row * 2 + 1];
+    if (!(px + py == px + py)) return false;      // NaN point = no collision point
+    const int e = row / a.TO, t = row - e * a.TO;
+    if (a.scene_alive && !a.scene_alive[a.scene_of[a.env_agent[e]]]) return false;
+    const float* c = a.fine + ((size_t)a.env_agent[e] * a.TO + t) * 4;
+    dx = c[0] - px;
+    dy = c[1] - py;
+    d = sqrtf(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)));
+    pd = a.pdist[e];
+    return true;
+}
+
+// -log N(z; mu, var) per element as losses/common.py:26-41 evaluates it in fp32
+__device__ __forceinline__ float prior_nll(float z, float mu, float var) {
+    const float dz = z - mu;
+    return -(-logf(sqrtf(var)) - 0.91893853320467267f - (dz * dz) / (2.0f * var));
+}
+__device__ __forceinline__ float init_sq(float z, float init) {
+    const float di = init - z;
+    return di * di;
+}
+// AdvGenLoss: weight of a latent row's prior / init term, blended by its re-weight (reference :160-167, :227-231)
+__device__ __forceinline__ float atk_blend(float rw, float w, float w_atk) { return rw * w + (1.0f - rw) * w_atk; }
+__device__ __forceinline__ bool latent_row_alive(const AdvArgs& A, int r) {
+    return !(A.scene_alive && !A.scene_alive[A.a.scene_of[A.nonego[r]]]);
+}
+__device__ __forceinline__ double masked_mean(double sum, double count) { return sum / (count < 1.0 ? 1.0 : count); }
+
+// block-wide reductions of a 256-thread workgroup in a fixed order (wave tree, then the four waves pairwise)
+__device__ __forceinline__ double sum_waves_d(const double* w) { return (w[0] + w[1]) + (w[2] + w[3]); }
 __device__ __forceinline__ double block_sum_d(double v, double* s_red, int tid) {
     v = wave_sum_d(v);
     __syncthreads();
     if ((tid & 63) == 0) s_red[tid >> 6] = v;
     __syncthreads();
-    return (s_red[0] + s_red[1]) + (s_red[2] + s_red[3]);
+    return sum_waves_d(s_red);
 }
 __device__ __forceinline__ float block_max_f(float v, float* s_red, int tid) {
     v = wave_max(v);
@@ -724,6 +541,251 @@ __device__ __forceinline__ float block_max_f(float v, float* s_red, int tid) {
     if ((tid & 63) == 0) s_red[tid >> 6] = v;
     __syncthreads();
     return fmaxf(fmaxf(s_red[0], s_red[1]), fmaxf(s_red[2], s_red[3]));
+}
+
+// batch-wide "everybody is always behind" test -> variant 1 (no behind mask); every workgroup that needs it forms it itself
+__device__ __forceinline__ int adv_select(const int32_t* scene_flag, int B, int use_infront, int tid) {
+    __shared__ int s_all;
+    if (tid == 0) s_all = use_infront ? 1 : 0;
+    __syncthreads();
+    int all = 1;
+    for (int b = tid; b < B; b += blockDim.x) all &= scene_flag[b];
+    if (!all) s_all = 0;                 // (every writer stores the same value)
+    __syncthreads();
+    return s_all;
+}
+
+// Per-workgroup partial sums of the LossSum terms of either objective.  AdvGenLoss (ADV) picks the soft-min variant first, sends
+// the planner-involving slots (slot_ne >= 0) to their own re-weighted accumulator, blends the weight of every latent row by
+// its re-weight and skips the rows of quarantined scenes; the AvoidCollLoss form compiles none of that.
+template <bool ADV>
+__global__ __launch_bounds__(256) void loss_partial_kernel(LossArgs<ADV> A, double* __restrict__ partial) {
+    constexpr int NTERMS = ADV ? ADV_TERMS : AV_TERMS;
+    __shared__ double s_red[NTERMS][4];
+    const AvoidArgs& a = avoid_part(A);
+    const int tid = threadIdx.x;
+    const float* rew = nullptr;
+    float w_plan = 0.f;
+    if constexpr (ADV) {
+        rew = A.rew2 + (size_t)adv_select(A.scene_flag, A.B, A.use_infront, tid) * a.NE;
+        w_plan = A.w_plan;
+    }
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    const long long g0 = (long long)blockIdx.x * blockDim.x + tid;
+    double acc[NTERMS] = {};
+    if (a.w_veh > 0.f || w_plan > 0.f) {
+        // (t, slot) walked with 32-bit indices: slot fastest, so pen / hit reads are contiguous and `valid` stays in L1
+        const int per_t = (a.P + NT_AV - 1) / NT_AV;                 // slot chunks of one time sample
+        const long long nchunk = (long long)a.TO * per_t;
+        for (long long ch = blockIdx.x; ch < nchunk; ch += gridDim.x) {
+            const int t = (int)(ch / per_t), slot = (int)(ch - (long long)t * per_t) * NT_AV + tid;
+            if (slot < a.P) {
+                const size_t i = (size_t)t * a.P + slot;
+                if (a.hit[i] && a.valid[slot]) {          // (pen is only valid behind hit)
+                    bool planner = false;
+                    if constexpr (ADV) {
+                        const int ne = A.slot_ne[slot];
+                        planner = ne >= 0;
+                        if (planner && w_plan > 0.f) { acc[S_PLAN] += (double)(a.pen[i] * rew[ne]); acc[S_PLAN_N] += 1.0; }
+                    }
+                    if (!planner && a.w_veh > 0.f) { acc[S_VEH] += (double)a.pen[i]; acc[S_VEH_N] += 1.0; }
+                }
+            }
+        }
+    }
+    if (a.w_env > 0.f) {
+        const long long n = (long long)a.NE * a.TO;
+        for (long long i = g0; i < n; i += stride) {
+            float dx, dy, d, pd;
+            if (env_row(a, (int)i, dx, dy, d, pd)) { acc[S_ENV] += (double)(1.0f - d / pd); acc[S_ENV_N] += 1.0; }
+        }
+    }
+    if (a.w_prior > 0.f || a.w_init > 0.f) {
+        const long long n = (long long)a.NZ * a.D;
+        for (long long i = g0; i < n; i += stride) {
+            float rw = 0.f;
+            if constexpr (ADV) {
+                const int r = (int)(i / a.D);
+                if (!latent_row_alive(A, r)) continue;
+                rw = rew[r];
+            }
+            const float z = a.z[i];
+            if (a.w_prior > 0.f) {
+                const float nll = prior_nll(z, a.mu[i], a.var[i]);
+                if constexpr (ADV) acc[S_PRIOR] += (double)(nll * atk_blend(rw, a.w_prior, A.w_prior_atk));
+                else acc[S_PRIOR] += (double)nll;
+            }
+            if (a.w_init > 0.f) {
+                const float sq = init_sq(z, a.init_z[i]);
+                if constexpr (ADV) acc[S_INIT] += (double)(sq * atk_blend(rw, a.w_init, A.w_init_atk));
+                else acc[S_INIT] += (double)sq;
+            }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < NTERMS; ++k) acc[k] = wave_sum_d(acc[k]);
+    if ((tid & 63) == 0)
+        for (int k = 0; k < NTERMS; ++k) s_red[k][tid >> 6] = acc[k];
+    __syncthreads();
+    if (tid < NTERMS) partial[(size_t)blockIdx.x * NTERMS + tid] = sum_waves_d(s_red[tid]);
+}
+
+// s[k] = sums[k] = term k added over the workgroup partials, one wave: lanes stride over the partials, then a shuffle tree -- a
+// fixed order (deterministic), 16 steps instead of 1024
+template <int NTERMS>
+__device__ __forceinline__ void sum_partials(const double* __restrict__ partial, int nblocks, int tid, double* s, double* sums) {
+    for (int k = 0; k < NTERMS; ++k) {
+        double v = 0.0;
+        for (int b = tid; b < nblocks; b += 64) v += partial[(size_t)b * NTERMS + k];
+        v = wave_sum_d(v);
+        if (tid == 0) { s[k] = v; sums[k] = v; }
+    }
+}
+
+__global__ __launch_bounds__(64) void avoid_final_kernel(AvoidArgs a, const double* __restrict__ partial, int nblocks,
+                                                           double* __restrict__ sums, float* __restrict__ out) {
+    __shared__ double s[AV_TERMS];
+    const int tid = threadIdx.x;
+    sum_partials<AV_TERMS>(partial, nblocks, tid, s, sums);
+    __syncthreads();
+    if (tid == 0) {
+        const double veh = masked_mean(s[S_VEH], s[S_VEH_N]);
+        const double env = masked_mean(s[S_ENV], s[S_ENV_N]);
+        const double pri = a.prior_den > 0.f ? s[S_PRIOR] / (double)a.prior_den : 0.0;
+        const double ini = a.init_den > 0.f ? s[S_INIT] / (double)a.init_den : 0.0;
+        double loss = 0.0;
+        if (a.w_veh > 0.f) loss += (double)a.w_veh * veh;
+        if (a.w_env > 0.f) loss += (double)a.w_env * env;
+        if (a.w_prior > 0.f) loss += (double)a.w_prior * pri;
+        if (a.w_init > 0.f) loss += (double)a.w_init * ini;
+        out[AO_LOSS] = (float)loss;
+        out[AO_VEH] = (float)veh;
+        out[AO_ENV] = (float)env;
+        out[AO_PRIOR] = (float)pri;
+        out[AO_INIT] = (float)ini;
+        out[AO_VEH_N] = (float)s[S_VEH_N];
+        out[AO_ENV_N] = (float)s[S_ENV_N];
+        for (int k = AO_END; k < AO_SIZE; ++k) out[k] = 0.f;
+    }
+}
+
+__global__ __launch_bounds__(64) void adv_final_kernel(AdvArgs A, const double* __restrict__ partial, int nblocks,
+                                                         double* __restrict__ sums, int32_t* __restrict__ sel_out,
+                                                         float* __restrict__ out, float* __restrict__ soft,
+                                                         float* __restrict__ rew) {
+    __shared__ double s[ADV_LOCAL];
+    const AvoidArgs& a = A.a;
+    const int tid = threadIdx.x;
+    const int sel = adv_select(A.scene_flag, A.B, A.use_infront, tid);
+    sum_partials<ADV_TERMS>(partial, nblocks, tid, s, sums);
+    {
+        double v = 0.0, rows = 0.0, scenes = 0.0;
+        for (int b = tid; b < A.B; b += 64) {
+            v += (double)A.crash2[(size_t)sel * A.B + b];
+            if (!A.scene_alive || A.scene_alive[b]) { scenes += 1.0; rows += (double)(A.ne_ptr[b + 1] - A.ne_ptr[b]); }
+        }
+        v = wave_sum_d(v);
+        rows = wave_sum_d(rows);
+        scenes = wave_sum_d(scenes);
+        if (tid == 0) { s[S_CRASH] = v; s[S_ROWS] = sums[S_ROWS] = rows; s[S_SCENES] = sums[S_SCENES] = scenes; }
+    }
+    // the selected soft-min weights and re-weights, for the caller (return_mins, logging)
+    for (long long i = tid; i < (long long)a.NE * A.NT; i += 64) soft[i] = A.soft2[(size_t)sel * a.NE * A.NT + i];
+    for (int i = tid; i < a.NE; i += 64) {
+        const float rv = A.rew2[(size_t)sel * a.NE + i];
+        rew[i] = rv;
+        A.rew_sel[i] = rv;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        const double veh = masked_mean(s[S_VEH], s[S_VEH_N]);
+        const double env = masked_mean(s[S_ENV], s[S_ENV_N]);
+        const double plan = masked_mean(s[S_PLAN], s[S_PLAN_N]);
+        // means over the latent rows / scenes that are in the batch: all of them, or the alive ones (= the batch rebuilt
+        // without the quarantined scenes, which is what the reference's batch_size-1 runs amount to)
+        const double pri = s[S_ROWS] > 0.0 ? s[S_PRIOR] / s[S_ROWS] : 0.0;
+        const double ini = s[S_INIT];
+        const double crash = s[S_SCENES] > 0.0 ? s[S_CRASH] / s[S_SCENES] : 0.0;
+        double loss = 0.0;
+        if (a.w_init > 0.f) loss += ini;
+        if (a.w_prior > 0.f) loss += pri;
+        if (a.w_veh > 0.f) loss += (double)a.w_veh * veh;
+        if (A.w_plan > 0.f) loss += (double)A.w_plan * plan;
+        if (a.w_env > 0.f) loss += (double)a.w_env * env;
+        if (A.w_crash > 0.f) loss += (double)A.w_crash * crash;
+        sel_out[0] = sel;
+        out[DO_LOSS] = (float)loss;
+        out[DO_VEH] = (float)veh;
+        out[DO_PLAN] = (float)plan;
+        out[DO_ENV] = (float)env;
+        out[DO_PRIOR] = (float)pri;
+        out[DO_INIT] = (float)ini;
+        out[DO_CRASH] = (float)crash;
+        out[DO_VEH_N] = (float)s[S_VEH_N];
+        out[DO_PLAN_N] = (float)s[S_PLAN_N];
+        out[DO_ENV_N] = (float)s[S_ENV_N];
+        out[DO_SEL] = (float)sel;
+        for (int k = DO_END; k < DO_SIZE; ++k) out[k] = 0.f;
+    }
+}
+
+// The (NA, TO) rows of d_fine, then the (NZ, D) elements of d_z.  d_fine gets the environment term -- every row is written, zeros
+// where the agent takes no environment term or has no collision point, so the vehicle term can accumulate on top without a
+// memset; only the latent half differs between the objectives.
+template <bool ADV>
+__global__ __launch_bounds__(256) void loss_grad_kernel(LossArgs<ADV> A, const int32_t* __restrict__ env_of_agent,
+                                                          const double* __restrict__ sums, const float* __restrict__ d_loss,
+                                                          float* __restrict__ d_fine, float* __restrict__ d_z) {
+    const AvoidArgs& a = avoid_part(A);
+    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long long n_rows = (long long)a.NA * a.TO;
+    const float gl = d_loss[0];
+    if (idx < n_rows) {
+        const int ag = (int)(idx / a.TO), t = (int)(idx - (long long)ag * a.TO);
+        float gx = 0.f, gy = 0.f;
+        const int e = (a.w_env > 0.f && env_of_agent) ? env_of_agent[ag] : -1;
+        if (e >= 0) {
+            float dx, dy, d, pd;
+            if (env_row(a, e * a.TO + t, dx, dy, d, pd) && d > 0.f) {
+                const float gs = (float)masked_mean((double)gl * (double)a.w_env, sums[S_ENV_N]);
+                const float k = -gs / (d * pd);      // pen = 1 - d / pd  ->  d pen / d c = -(c - p) / (d * pd)
+                gx = k * dx;
+                gy = k * dy;
+            }
+        }
+        float* o = d_fine + (size_t)idx * 4;
+        o[0] = gx; o[1] = gy; o[2] = 0.f; o[3] = 0.f;
+        return;
+    }
+    const long long i = idx - n_rows;
+    if (i < (long long)a.NZ * a.D) {
+        const float z = a.z[i];
+        float g = 0.f;
+        if constexpr (ADV) {
+            const int r = (int)(i / a.D);
+            const float rw = A.rew_sel[r];
+            if (latent_row_alive(A, r)) {
+                if (a.w_prior > 0.f) g += gl * atk_blend(rw, a.w_prior, A.w_prior_atk) / (float)sums[S_ROWS] * ((z - a.mu[i]) / a.var[i]);
+                if (a.w_init > 0.f) g += gl * atk_blend(rw, a.w_init, A.w_init_atk) * (2.0f * (z - a.init_z[i]));
+            }
+        } else {
+            if (a.w_prior > 0.f) g += gl * a.w_prior / a.prior_den * ((z - a.mu[i]) / a.var[i]);
+            if (a.w_init > 0.f) g += gl * a.w_init / a.init_den * (2.0f * (z - a.init_z[i]));
+        }
+        d_z[i] = g;
+    }
+}
+
+// entry e = (non-ego agent, crash time sample) of scene b, whose non-ego rows start at a0: attacker position minus target position
+// and its length; returns the offset of the attacker's pose in traj / d_traj and leaves the target's pose in q
+__device__ __forceinline__ size_t crash_entry(const AdvArgs& A, int b, int a0, int e, const float*& q, float& dx, float& dy, float& d) {
+    const int al = e / A.NT, t = e - al * A.NT;
+    const size_t at = ((size_t)A.nonego[a0 + al] * A.T + A.t0 + t) * 4;
+    q = A.tgt + ((size_t)b * A.T + A.t0 + t) * 4;
+    dx = A.traj[at] - q[0];
+    dy = A.traj[at + 1] - q[1];
+    d = sqrtf(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)));
+    return at;
 }
 
 // one workgroup per scene
@@ -749,16 +811,14 @@ __global__ __launch_bounds__(256) void adv_crash_kernel(AdvArgs A) {
     if (tid < 64) s_nb[tid] = 0;
     __syncthreads();
     for (int e = tid; e < E; e += 256) {
-        const int al = e / NT, t = e - al * NT;
-        const float* p = A.traj + ((size_t)A.nonego[a0 + al] * A.T + A.t0 + t) * 4;
-        const float* q = A.tgt + ((size_t)b * A.T + A.t0 + t) * 4;
-        const float dx = p[0] - q[0], dy = p[1] - q[1];
-        const float d = sqrtf(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)));
+        const float* q;
+        float dx, dy, d;
+        crash_entry(A, b, a0, e, q, dx, dy, d);
         s_d[e] = d;
         if (A.use_infront) {
             // behind <=> (atk - tgt) / |atk - tgt| . heading(tgt) < threshold   (reference :646-673); NaN compares false
             const float dot = __fadd_rn(__fmul_rn(dx / d, q[2]), __fmul_rn(dy / d, q[3]));
-            if (!(dot < A.infront)) atomicAdd(&s_nb[al], 1);
+            if (!(dot < A.infront)) atomicAdd(&s_nb[e / NT], 1);
         }
     }
     __syncthreads();
@@ -768,24 +828,23 @@ __global__ __launch_bounds__(256) void adv_crash_kernel(AdvArgs A) {
         A.scene_flag[b] = all_always;            // (an empty scene leaves 1: it does not veto the batch-wide test)
     }
     for (int v = 0; v < 2; ++v) {
-        float mx = -3.0e38f;
-        bool any = false;
-        for (int e = tid; e < E; e += 256) {
+        // entry e is out of the soft-min: its agent is always behind (variant 0 only) or not among the selected attackers
+        auto masked = [&](int e) {
             const int al = e / NT;
-            const bool masked = (v == 0 && A.use_infront && s_nb[al] == 0) || (A.atk_mask && !A.atk_mask[a0 + al]);
+            return (v == 0 && A.use_infront && s_nb[al] == 0) || (A.atk_mask && !A.atk_mask[a0 + al]);
+        };
+        float mx = -3.0e38f;
+        for (int e = tid; e < E; e += 256) {
             const float d = s_d[e];
-            if (!masked && !(d != d)) { mx = fmaxf(mx, -d); any = true; }
+            if (!masked(e) && !(d != d)) mx = fmaxf(mx, -d);
         }
         mx = block_max_f(mx, s_redf, tid);
         double den = 0.0;
         for (int e = tid; e < E; e += 256) {
-            const int al = e / NT;
-            const bool masked = (v == 0 && A.use_infront && s_nb[al] == 0) || (A.atk_mask && !A.atk_mask[a0 + al]);
-            const float ex = masked ? 0.f : expf(-s_d[e] - mx);
+            const float ex = masked(e) ? 0.f : expf(-s_d[e] - mx);
             s_s[e] = ex;
             den += (double)ex;
         }
-        (void)any;
         den = block_sum_d(den, s_redd, tid);
         const bool dead = !(den > 0.0) || mx <= -3.0e38f;          // nothing unmasked (or NaN distances): all weights 0 (:134-135)
         double cr = 0.0;
@@ -807,186 +866,6 @@ __global__ __launch_bounds__(256) void adv_crash_kernel(AdvArgs A) {
     }
 }
 
-// batch-wide "everybody is always behind" test -> variant 1 (no behind mask); every workgroup that needs it forms it itself
-__device__ __forceinline__ int adv_select(const int32_t* scene_flag, int B, int use_infront, int tid) {
-    __shared__ int s_all;
-    if (tid == 0) s_all = use_infront ? 1 : 0;
-    __syncthreads();
-    int all = 1;
-    for (int b = tid; b < B; b += blockDim.x) all &= scene_flag[b];
-    if (!all) s_all = 0;                 // (every writer stores the same value)
-    __syncthreads();
-    return s_all;
-}
-
-__global__ __launch_bounds__(256) void adv_partial_kernel(AdvArgs A, double* __restrict__ partial) {
-    __shared__ double s_red[4][ADV_TERMS];
-    const AvoidArgs& a = A.a;
-    const int tid = threadIdx.x;
-    const int sel = adv_select(A.scene_flag, A.B, A.use_infront, tid);
-    const float* rew = A.rew2 + (size_t)sel * a.NE;
-    const long long stride = (long long)gridDim.x * blockDim.x;
-    const long long g0 = (long long)blockIdx.x * blockDim.x + tid;
-    double acc[ADV_TERMS] = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (a.w_veh > 0.f || A.w_plan > 0.f) {
-        const int per_t = (a.P + NT_AV - 1) / NT_AV;
-        const long long nchunk = (long long)a.TO * per_t;
-        for (long long ch = blockIdx.x; ch < nchunk; ch += gridDim.x) {
-            const int t = (int)(ch / per_t), slot = (int)(ch - (long long)t * per_t) * NT_AV + tid;
-            if (slot < a.P) {
-                const size_t i = (size_t)t * a.P + slot;
-                if (a.hit[i] && a.valid[slot]) {
-                    const int ne = A.slot_ne[slot];
-                    if (ne >= 0) {
-                        if (A.w_plan > 0.f) { acc[6] += (double)(a.pen[i] * rew[ne]); acc[7] += 1.0; }
-                    } else if (a.w_veh > 0.f) {
-                        acc[0] += (double)a.pen[i];
-                        acc[1] += 1.0;
-                    }
-                }
-            }
-        }
-    }
-    if (a.w_env > 0.f) {
-        const long long n = (long long)a.NE * a.TO;
-        for (long long i = g0; i < n; i += stride) {
-            float dx, dy, d, pd;
-            if (env_row(a, (int)i, dx, dy, d, pd)) { acc[2] += (double)(1.0f - d / pd); acc[3] += 1.0; }
-        }
-    }
-    if (a.w_prior > 0.f || a.w_init > 0.f) {
-        const long long n = (long long)a.NZ * a.D;
-        for (long long i = g0; i < n; i += stride) {
-            const int r = (int)(i / a.D);
-            if (A.scene_alive && !A.scene_alive[a.scene_of[A.nonego[r]]]) continue;
-            const float rw = rew[r];
-            const float z = a.z[i];
-            if (a.w_prior > 0.f) {
-                const float m = a.mu[i], v = a.var[i];
-                const float dz = z - m;
-                const float lp = -logf(sqrtf(v)) - 0.91893853320467267f - (dz * dz) / (2.0f * v);
-                acc[4] -= (double)(lp * (rw * a.w_prior + (1.0f - rw) * A.w_prior_atk));
-            }
-            if (a.w_init > 0.f) {
-                const float di = a.init_z[i] - z;
-                acc[5] += (double)((di * di) * (rw * a.w_init + (1.0f - rw) * A.w_init_atk));
-            }
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < ADV_TERMS; ++k) acc[k] = wave_sum_d(acc[k]);
-    if ((tid & 63) == 0)
-        for (int k = 0; k < ADV_TERMS; ++k) s_red[tid >> 6][k] = acc[k];
-    __syncthreads();
-    if (tid < ADV_TERMS) partial[(size_t)blockIdx.x * ADV_TERMS + tid] = (s_red[0][tid] + s_red[1][tid]) + (s_red[2][tid] + s_red[3][tid]);
-}
-
-__global__ __launch_bounds__(64) void adv_final_kernel(AdvArgs A, const double* __restrict__ partial, int nblocks,
-                                                         double* __restrict__ sums, int32_t* __restrict__ sel_out,
-                                                         float* __restrict__ out, float* __restrict__ soft,
-                                                         float* __restrict__ rew) {
-    __shared__ double s[ADV_TERMS + 3];
-    const AvoidArgs& a = A.a;
-    const int tid = threadIdx.x;
-    const int sel = adv_select(A.scene_flag, A.B, A.use_infront, tid);
-    for (int k = 0; k < ADV_TERMS; ++k) {
-        double v = 0.0;
-        for (int b = tid; b < nblocks; b += 64) v += partial[(size_t)b * ADV_TERMS + k];
-        v = wave_sum_d(v);
-        if (tid == 0) { s[k] = v; sums[k] = v; }
-    }
-    {
-        double v = 0.0, rows = 0.0, scenes = 0.0;
-        for (int b = tid; b < A.B; b += 64) {
-            v += (double)A.crash2[(size_t)sel * A.B + b];
-            if (!A.scene_alive || A.scene_alive[b]) { scenes += 1.0; rows += (double)(A.ne_ptr[b + 1] - A.ne_ptr[b]); }
-        }
-        v = wave_sum_d(v);
-        rows = wave_sum_d(rows);
-        scenes = wave_sum_d(scenes);
-        if (tid == 0) { s[ADV_TERMS] = v; s[ADV_TERMS + 1] = rows; s[ADV_TERMS + 2] = scenes; sums[8] = rows; sums[9] = scenes; }
-    }
-    // the selected soft-min weights and re-weights, for the caller (return_mins, logging)
-    for (long long i = tid; i < (long long)a.NE * A.NT; i += 64) soft[i] = A.soft2[(size_t)sel * a.NE * A.NT + i];
-    for (int i = tid; i < a.NE; i += 64) {
-        const float rv = A.rew2[(size_t)sel * a.NE + i];
-        rew[i] = rv;
-        A.rew_sel[i] = rv;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        const double veh = s[0] / (s[1] < 1.0 ? 1.0 : s[1]);
-        const double env = s[2] / (s[3] < 1.0 ? 1.0 : s[3]);
-        const double plan = s[6] / (s[7] < 1.0 ? 1.0 : s[7]);
-        // means over the latent rows / scenes that are in the batch: all of them, or the alive ones (= the batch rebuilt
-        // without the quarantined scenes, which is what the reference's batch_size-1 runs amount to)
-        const double pri = s[ADV_TERMS + 1] > 0.0 ? s[4] / s[ADV_TERMS + 1] : 0.0;
-        const double ini = s[5];
-        const double crash = s[ADV_TERMS + 2] > 0.0 ? s[ADV_TERMS] / s[ADV_TERMS + 2] : 0.0;
-        double loss = 0.0;
-        if (a.w_init > 0.f) loss += ini;
-        if (a.w_prior > 0.f) loss += pri;
-        if (a.w_veh > 0.f) loss += (double)a.w_veh * veh;
-        if (A.w_plan > 0.f) loss += (double)A.w_plan * plan;
-        if (a.w_env > 0.f) loss += (double)a.w_env * env;
-        if (A.w_crash > 0.f) loss += (double)A.w_crash * crash;
-        sel_out[0] = sel;
-        out[0] = (float)loss;
-        out[1] = (float)veh;
-        out[2] = (float)plan;
-        out[3] = (float)env;
-        out[4] = (float)pri;
-        out[5] = (float)ini;
-        out[6] = (float)crash;
-        out[7] = (float)s[1];
-        out[8] = (float)s[7];
-        out[9] = (float)s[3];
-        out[10] = (float)sel;
-        for (int k = 11; k < 16; ++k) out[k] = 0.f;
-    }
-}
-
-// d_fine of the environment term (all rows written, like avoid_grad_kernel) and d_z
-__global__ __launch_bounds__(256) void adv_grad_kernel(AdvArgs A, const int32_t* __restrict__ env_of_agent,
-                                                         const double* __restrict__ sums, const int32_t* __restrict__ sel_p,
-                                                         const float* __restrict__ d_loss, float* __restrict__ d_fine,
-                                                         float* __restrict__ d_z) {
-    const AvoidArgs& a = A.a;
-    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    const long long n_rows = (long long)a.NA * a.TO;
-    const float gl = d_loss[0];
-    if (idx < n_rows) {
-        const int ag = (int)(idx / a.TO), t = (int)(idx - (long long)ag * a.TO);
-        float gx = 0.f, gy = 0.f;
-        const int e = (a.w_env > 0.f && env_of_agent) ? env_of_agent[ag] : -1;
-        if (e >= 0) {
-            float dx, dy, d, pd;
-            if (env_row(a, e * a.TO + t, dx, dy, d, pd) && d > 0.f) {
-                const double c = sums[3];
-                const float gs = (float)((double)gl * (double)a.w_env / (c < 1.0 ? 1.0 : c));
-                const float k = -gs / (d * pd);
-                gx = k * dx;
-                gy = k * dy;
-            }
-        }
-        float* o = d_fine + (size_t)idx * 4;
-        o[0] = gx; o[1] = gy; o[2] = 0.f; o[3] = 0.f;
-        return;
-    }
-    const long long i = idx - n_rows;
-    if (i < (long long)a.NZ * a.D) {
-        const int r = (int)(i / a.D);
-        const float rw = A.rew_sel[r];
-        const float z = a.z[i];
-        float g = 0.f;
-        if (!(A.scene_alive && !A.scene_alive[a.scene_of[A.nonego[r]]])) {
-            if (a.w_prior > 0.f) g += gl * (rw * a.w_prior + (1.0f - rw) * A.w_prior_atk) / (float)sums[8] * ((z - a.mu[i]) / a.var[i]);
-            if (a.w_init > 0.f) g += gl * (rw * a.w_init + (1.0f - rw) * A.w_init_atk) * (2.0f * (z - a.init_z[i]));
-        }
-        d_z[i] = g;
-    }
-}
-
 // crash term: L = w/B sum_b sum_e s_e d_e^2 with s = softmin(d) over the scene's unmasked entries
 //   dL/dd_e = w/B * s_e * (2 d_e + C_b - d_e^2),  C_b = sum_e s_e d_e^2;   dd/d(atk xy) = (atk - tgt) / d = -dd/d(tgt xy)
 // one workgroup per scene: adds into d_traj (non-ego rows, time >= t0; interp_bwd has written them) and writes d_tgt
@@ -998,14 +877,11 @@ __global__ __launch_bounds__(256) void adv_crash_bwd_kernel(AdvArgs A, const int
     const int sel = sel_p[0];
     const int a0 = A.ne_ptr[b], n = A.ne_ptr[b + 1] - a0, NT = A.NT, E = n * NT;
     const float C = A.crash2[(size_t)sel * A.B + b];
-    const float gw = A.w_crash > 0.f ? d_loss[0] * A.w_crash / (float)sums[9] : 0.f;      // (a quarantined scene has soft == 0 throughout)
+    const float gw = A.w_crash > 0.f ? d_loss[0] * A.w_crash / (float)sums[S_SCENES] : 0.f;      // (a quarantined scene has soft == 0 throughout)
     for (int e = tid; e < E; e += 256) {
-        const int al = e / NT, t = e - al * NT;
-        float* gp = d_traj + ((size_t)A.nonego[a0 + al] * A.T + A.t0 + t) * 4;
-        const float* p = A.traj + ((size_t)A.nonego[a0 + al] * A.T + A.t0 + t) * 4;
-        const float* q = A.tgt + ((size_t)b * A.T + A.t0 + t) * 4;
-        const float dx = p[0] - q[0], dy = p[1] - q[1];
-        const float d = sqrtf(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)));
+        const float* q;
+        float dx, dy, d;
+        float* gp = d_traj + crash_entry(A, b, a0, e, q, dx, dy, d);
         const float sft = A.soft2[((size_t)sel * A.a.NE + a0) * NT + e];
         float gx = 0.f, gy = 0.f;
         if (sft != 0.f && d > 0.f) {
@@ -1028,6 +904,45 @@ __global__ __launch_bounds__(256) void adv_crash_bwd_kernel(AdvArgs A, const int
     }
 }
 
+static AvoidArgs avoid_args(const StriveScenes* sc, const StriveAvoidColl* h, const AvoidWs& w, int TO, const float* z,
+                            const float* mu, const float* var) {
+    AvoidArgs a;
+    a.NA = sc->NA; a.TO = TO; a.P = h->P; a.NE = h->NE; a.NZ = h->NZ; a.D = h->D;
+    a.prior_den = h->prior_den; a.init_den = h->init_den;
+    a.fine = w.fine; a.pen = w.pen; a.hit = w.hit; a.valid = h->pair_valid;
+    a.env_agent = h->env_agent; a.pt = w.pt; a.pdist = h->env_pdist;
+    a.z = z; a.mu = mu; a.var = var; a.init_z = h->init_z;
+    a.w_veh = h->w_veh; a.w_env = h->w_env; a.w_prior = h->w_prior; a.w_init = h->w_init;
+    a.scene_alive = nullptr; a.scene_of = sc->scene_of;
+    return a;
+}
+
+static AdvArgs adv_args(const StriveScenes* sc, const StriveAdvGen* h, const AdvWs& w, int T, const float* traj, const float* tgt,
+                        const float* z, const float* mu, const float* var) {
+    AdvArgs A;
+    A.a = avoid_args(sc, &h->base, w.av, T * h->base.scale, z, mu, var);
+    A.B = sc->B; A.T = T; A.t0 = h->t0; A.NT = T - h->t0; A.use_infront = h->use_infront; A.infront = h->infront;
+    A.traj = traj; A.tgt = tgt; A.ne_ptr = h->ne_ptr; A.nonego = h->base.env_agent; A.slot_ne = h->slot_ne; A.atk_mask = h->atk_mask;
+    A.scene_alive = h->scene_alive; A.a.scene_alive = h->scene_alive;
+    A.w_crash = h->w_crash; A.w_plan = h->w_plan; A.w_prior_atk = h->w_prior_atk; A.w_init_atk = h->w_init_atk;
+    A.soft2 = w.soft2; A.rew2 = w.rew2; A.crash2 = w.crash2; A.scene_flag = w.scene_flag; A.rew_sel = w.rew_sel;
+    return A;
+}
+
+static int avoid_check(const StriveScenes* sc, const StriveAvoidColl* h, int T) {
+    STRIVE_CHECK_ARG(sc && h, "null argument");
+    STRIVE_CHECK_ARG(sc->NS == 1, "collision losses take one trajectory per agent");
+    STRIVE_CHECK_ARG(T > 0 && h->scale >= 1 && h->P >= 0 && h->NE >= 0 && h->NZ >= 0 && h->D >= 0, "bad sizes");
+    STRIVE_CHECK_ARG(h->i0 && h->i1 && h->w0 && h->w1, "null interpolation taps");
+    if (h->w_veh > 0.f) STRIVE_CHECK_ARG(h->pair_off && h->cent_x && h->rad && h->pair_valid, "null vehicle-term constants");
+    if (h->w_env > 0.f && h->NE > 0)
+        STRIVE_CHECK_ARG(h->env_agent && h->env_of_agent && h->env_lw && h->env_mapix && h->env_pdist && h->lin_l && h->lin_w &&
+                             h->gl > 0 && h->gw > 0,
+                         "null environment-term constants");
+    if (h->w_init > 0.f) STRIVE_CHECK_ARG(h->init_z, "null init_z");
+    return 0;
+}
+
 static int adv_check(const StriveScenes* sc, const StriveAdvGen* h, int T) {
     STRIVE_CHECK_ARG(sc && h, "null argument");
     if (int rc = avoid_check(sc, &h->base, T)) return rc;
@@ -1041,16 +956,102 @@ static int adv_check(const StriveScenes* sc, const StriveAdvGen* h, int T) {
     return 0;
 }
 
-static AdvArgs adv_args(const StriveScenes* sc, const StriveAdvGen* h, const AdvWs& w, int T, const float* traj, const float* tgt,
-                        const float* z, const float* mu, const float* var) {
-    AdvArgs A;
-    A.a = avoid_args(sc, &h->base, w.av, T * h->base.scale, z, mu, var);
-    A.B = sc->B; A.T = T; A.t0 = h->t0; A.NT = T - h->t0; A.use_infront = h->use_infront; A.infront = h->infront;
-    A.traj = traj; A.tgt = tgt; A.ne_ptr = h->ne_ptr; A.nonego = h->base.env_agent; A.slot_ne = h->slot_ne; A.atk_mask = h->atk_mask;
-    A.scene_alive = h->scene_alive; A.a.scene_alive = h->scene_alive;
-    A.w_crash = h->w_crash; A.w_plan = h->w_plan; A.w_prior_atk = h->w_prior_atk; A.w_init_atk = h->w_init_atk;
-    A.soft2 = w.soft2; A.rew2 = w.rew2; A.crash2 = w.crash2; A.scene_flag = w.scene_flag; A.rew_sel = w.rew_sel;
-    return A;
+// The stages both forwards open with: interp -> vehicle penalties (`veh`; far pairs culled on request, the pairs of scenes that
+// are not `alive` written as not colliding) -> collision points
+static int coll_forward_stages(const StriveScenes* sc, const StriveMap* map, const StriveAvoidColl* h, const float* traj, int T,
+                               const AvoidWs& w, bool veh, int cull, const uint8_t* alive, strive_stream_t stream) {
+    const int NA = sc->NA, TO = T * h->scale;
+    if (NA <= 0) return 0;
+    if (int rc = strive_interp_traj_fwd(traj, NA, T, TO, h->i0, h->i1, h->w0, h->w1, w.fine, stream)) return rc;
+    if (veh)
+        if (int rc = veh_coll_fwd_masked(sc, h->pair_off, h->P, w.fine, TO, h->cent_x, h->rad, h->buffer, alive, w.pen, w.hit, w.amin,
+                                         stream, cull))
+            return rc;
+    if (h->w_env > 0.f && h->NE > 0)
+        if (int rc = strive_coll_point_rows(map, w.fine, TO, h->env_agent, h->env_lw, h->env_mapix, h->NE, h->gl, h->gw, h->lin_l,
+                                            h->lin_w, w.pt, w.cnt, stream))
+            return rc;
+    return 0;
+}
+
+// workgroups of the partial-sum kernel: 2048 elements of the longest of its three walks each
+static int reduce_blocks(const StriveAvoidColl* h, int TO) {
+    long long work = (long long)TO * h->P;
+    if ((long long)h->NE * TO > work) work = (long long)h->NE * TO;
+    if ((long long)h->NZ * h->D > work) work = (long long)h->NZ * h->D;
+    const int nb = (int)((work + 2047) / 2048);
+    return nb < 1 ? 1 : (nb > AV_BLOCKS ? AV_BLOCKS : nb);
+}
+
+// The stages both backwards share once d_fine holds the environment term: the vehicle term's implicit gradient on top (`veh`;
+// AdvGenLoss passes slot_ne / rew_sel / w_plan for the planner pairs' second mean), then interp backward into d_traj
+static int coll_backward_stages(const StriveScenes* sc, const StriveAvoidColl* h, const AvoidWs& w, const double* sums,
+                                const float* traj, int T, const float* d_loss, float* d_traj, strive_stream_t stream, bool veh,
+                                const int32_t* slot_ne = nullptr, const float* rew_sel = nullptr, float w_plan = 0.f) {
+    const int NA = sc->NA, TO = T * h->scale;
+    if (veh) {
+        VehImplicit im;
+        im.hit = w.hit; im.valid = h->pair_valid; im.sums = sums; im.d_loss = d_loss; im.w = h->w_veh;
+        im.slot_ne = slot_ne; im.rew = rew_sel; im.w2 = w_plan;
+        const long long nv = (long long)NA * TO * VG;
+        hipLaunchKernelGGL(veh_coll_bwd_kernel<true>, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                           veh_args(sc, h->pair_off, h->P, w.fine, TO, h->cent_x, h->rad, h->buffer), (const float*)nullptr,
+                           (const uint8_t*)w.amin, w.d_fine, im);
+        STRIVE_CHECK_LAUNCH();
+    }
+    return strive_interp_traj_bwd(traj, w.d_fine, NA, T, TO, h->scale, h->i0, h->i1, h->w0, h->w1, d_traj, stream);
+}
+
+extern "C" size_t strive_avoid_coll_workspace_bytes(const StriveScenes* sc, const StriveAvoidColl* h, int32_t T) {
+    if (!sc || !h || T <= 0 || h->scale < 1) return 0;
+    return avoid_ws_bytes((size_t)sc->NA, (size_t)T * h->scale, (size_t)h->P, (size_t)h->NE);
+}
+
+extern "C" int strive_avoid_coll_fwd(const StriveScenes* sc, const StriveMap* map, const StriveAvoidColl* h, const float* traj,
+                                     int32_t T, const float* z, const float* mu, const float* var, float* out, void* ws,
+                                     size_t ws_bytes, strive_stream_t stream) {
+    if (int rc = avoid_check(sc, h, T)) return rc;
+    STRIVE_CHECK_ARG(traj && out && ws, "null argument");
+    if (h->w_prior > 0.f) STRIVE_CHECK_ARG(z && mu && var, "null latent tensors");
+    if (h->w_init > 0.f) STRIVE_CHECK_ARG(z, "null latent tensors");
+    if (h->w_env > 0.f && h->NE > 0) STRIVE_CHECK_ARG(map, "null map");
+    const int NA = sc->NA, TO = T * h->scale;
+    STRIVE_CHECK_ARG(ws_bytes >= avoid_ws_bytes(NA, TO, h->P, h->NE), "workspace too small");
+    StriveArena ar(ws, ws_bytes);
+    const AvoidWs w = avoid_layout(ar, NA, TO, h->P, h->NE);
+    hipStream_t st = (hipStream_t)stream;
+    if (int rc = coll_forward_stages(sc, map, h, traj, T, w, h->w_veh > 0.f && h->P > 0, /*cull=*/1, nullptr, stream)) return rc;
+    AvoidArgs a = avoid_args(sc, h, w, TO, z, mu, var);
+    if (h->P == 0) a.w_veh = 0.f;          // nothing to sum; the weight is re-applied below (mean of nothing = 0)
+    if (h->NE == 0) a.w_env = 0.f;
+    const int nb = reduce_blocks(h, TO);
+    hipLaunchKernelGGL(loss_partial_kernel<false>, dim3(nb), dim3(256), 0, st, a, w.partial);
+    STRIVE_CHECK_LAUNCH();
+    hipLaunchKernelGGL(avoid_final_kernel, dim3(1), dim3(64), 0, st, a, (const double*)w.partial, nb, w.sums, out);
+    STRIVE_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int strive_avoid_coll_bwd(const StriveScenes* sc, const StriveAvoidColl* h, const float* traj, int32_t T,
+                                     const float* z, const float* mu, const float* var, const float* d_loss, void* ws,
+                                     size_t ws_bytes, float* d_traj, float* d_z, strive_stream_t stream) {
+    if (int rc = avoid_check(sc, h, T)) return rc;
+    STRIVE_CHECK_ARG(traj && d_loss && ws && d_traj, "null argument");
+    const int NA = sc->NA, TO = T * h->scale;
+    STRIVE_CHECK_ARG(ws_bytes >= avoid_ws_bytes(NA, TO, h->P, h->NE), "workspace too small");
+    if (NA == 0) return 0;
+    StriveArena ar(ws, ws_bytes);
+    const AvoidWs w = avoid_layout(ar, NA, TO, h->P, h->NE);
+    AvoidArgs a = avoid_args(sc, h, w, TO, z, mu, var);
+    if (h->NE == 0) a.w_env = 0.f;
+    const bool latent = (h->w_prior > 0.f || h->w_init > 0.f) && h->D > 0;
+    if (latent) STRIVE_CHECK_ARG(z && d_z && (h->w_prior <= 0.f || (mu && var)), "null latent tensors");
+    if (!latent) a.D = 0;
+    const long long n = (long long)NA * TO + (long long)a.NZ * a.D;
+    hipLaunchKernelGGL(loss_grad_kernel<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a, h->env_of_agent,
+                       (const double*)w.sums, d_loss, w.d_fine, d_z);
+    STRIVE_CHECK_LAUNCH();
+    return coll_backward_stages(sc, h, w, w.sums, traj, T, d_loss, d_traj, stream, h->w_veh > 0.f && h->P > 0);
 }
 
 extern "C" size_t strive_adv_gen_workspace_bytes(const StriveScenes* sc, const StriveAdvGen* h, int32_t T) {
@@ -1068,20 +1069,11 @@ extern "C" int strive_adv_gen_fwd(const StriveScenes* sc, const StriveMap* map, 
     if (hb->w_env > 0.f && hb->NE > 0) STRIVE_CHECK_ARG(map, "null map");
     const int NA = sc->NA, TO = T * hb->scale, NT = T - h->t0;
     STRIVE_CHECK_ARG(ws_bytes >= adv_ws_bytes(NA, TO, hb->P, hb->NE, NT, sc->B), "workspace too small");
-    AdvWs w = adv_carve(ws, ws_bytes, NA, TO, hb->P, hb->NE, NT, sc->B);
+    StriveArena ar(ws, ws_bytes);
+    const AdvWs w = adv_layout(ar, NA, TO, hb->P, hb->NE, NT, sc->B);
     hipStream_t st = (hipStream_t)stream;
     const bool veh = (hb->w_veh > 0.f || h->w_plan > 0.f) && hb->P > 0;
-    if (NA > 0) {
-        if (int rc = strive_interp_traj_fwd(traj, NA, T, TO, hb->i0, hb->i1, hb->w0, hb->w1, w.av.fine, stream)) return rc;
-        if (veh)
-            if (int rc = veh_coll_fwd_masked(sc, hb->pair_off, hb->P, w.av.fine, TO, hb->cent_x, hb->rad, hb->buffer, h->scene_alive,
-                                             w.av.pen, w.av.hit, w.av.amin, stream))
-                return rc;
-        if (hb->w_env > 0.f && hb->NE > 0)
-            if (int rc = strive_coll_point_rows(map, w.av.fine, TO, hb->env_agent, hb->env_lw, hb->env_mapix, hb->NE, hb->gl, hb->gw,
-                                                hb->lin_l, hb->lin_w, w.av.pt, w.av.cnt, stream))
-                return rc;
-    }
+    if (int rc = coll_forward_stages(sc, map, hb, traj, T, w.av, veh, /*cull=*/0, h->scene_alive, stream)) return rc;
     AdvArgs A = adv_args(sc, h, w, T, traj, tgt, z, mu, var);
     if (!veh) { A.a.w_veh = 0.f; A.w_plan = 0.f; }
     if (hb->NE == 0) A.a.w_env = 0.f;
@@ -1089,12 +1081,8 @@ extern "C" int strive_adv_gen_fwd(const StriveScenes* sc, const StriveMap* map, 
         hipLaunchKernelGGL(adv_crash_kernel, dim3(sc->B), dim3(256), 0, st, A);
         STRIVE_CHECK_LAUNCH();
     }
-    long long work = (long long)TO * hb->P;
-    if ((long long)hb->NE * TO > work) work = (long long)hb->NE * TO;
-    if ((long long)hb->NZ * hb->D > work) work = (long long)hb->NZ * hb->D;
-    int nb = (int)((work + 2047) / 2048);
-    nb = nb < 1 ? 1 : (nb > AV_BLOCKS ? AV_BLOCKS : nb);
-    hipLaunchKernelGGL(adv_partial_kernel, dim3(nb), dim3(256), 0, st, A, w.partial);
+    const int nb = reduce_blocks(hb, TO);
+    hipLaunchKernelGGL(loss_partial_kernel<true>, dim3(nb), dim3(256), 0, st, A, w.partial);
     STRIVE_CHECK_LAUNCH();
     hipLaunchKernelGGL(adv_final_kernel, dim3(1), dim3(64), 0, st, A, (const double*)w.partial, nb, w.sums, w.sel, out, soft, rew);
     STRIVE_CHECK_LAUNCH();
@@ -1110,26 +1098,18 @@ extern "C" int strive_adv_gen_bwd(const StriveScenes* sc, const StriveAdvGen* h,
     const int NA = sc->NA, TO = T * hb->scale, NT = T - h->t0;
     STRIVE_CHECK_ARG(ws_bytes >= adv_ws_bytes(NA, TO, hb->P, hb->NE, NT, sc->B), "workspace too small");
     if (NA == 0) return 0;
-    AdvWs w = adv_carve(ws, ws_bytes, NA, TO, hb->P, hb->NE, NT, sc->B);
+    StriveArena ar(ws, ws_bytes);
+    const AdvWs w = adv_layout(ar, NA, TO, hb->P, hb->NE, NT, sc->B);
     hipStream_t st = (hipStream_t)stream;
     AdvArgs A = adv_args(sc, h, w, T, traj, tgt, z, mu, var);
     const bool veh = (hb->w_veh > 0.f || h->w_plan > 0.f) && hb->P > 0;
     if (hb->NE == 0) A.a.w_env = 0.f;
     const long long n = (long long)NA * TO + (long long)A.a.NZ * A.a.D;
-    hipLaunchKernelGGL(adv_grad_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, A, hb->env_of_agent,
-                       (const double*)w.sums, (const int32_t*)w.sel, d_loss, w.av.d_fine, d_z);
+    hipLaunchKernelGGL(loss_grad_kernel<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, A, hb->env_of_agent,
+                       (const double*)w.sums, d_loss, w.av.d_fine, d_z);
     STRIVE_CHECK_LAUNCH();
-    if (veh) {
-        VehImplicit im;
-        im.hit = w.av.hit; im.valid = hb->pair_valid; im.sums = w.sums; im.d_loss = d_loss; im.w = hb->w_veh;
-        im.slot_ne = h->slot_ne; im.rew = w.rew_sel; im.w2 = h->w_plan;
-        const long long nv = (long long)NA * TO * VG;
-        hipLaunchKernelGGL(veh_coll_bwd_kernel<true>, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, st,
-                           veh_args(sc, hb->pair_off, hb->P, w.av.fine, TO, hb->cent_x, hb->rad, hb->buffer), (const float*)nullptr,
-                           (const uint8_t*)w.av.amin, w.av.d_fine, im);
-        STRIVE_CHECK_LAUNCH();
-    }
-    if (int rc = strive_interp_traj_bwd(traj, w.av.d_fine, NA, T, TO, hb->scale, hb->i0, hb->i1, hb->w0, hb->w1, d_traj, stream)) return rc;
+    if (int rc = coll_backward_stages(sc, hb, w.av, w.sums, traj, T, d_loss, d_traj, stream, veh, h->slot_ne, w.rew_sel, h->w_plan))
+        return rc;
     if (sc->B > 0) {
         hipLaunchKernelGGL(adv_crash_bwd_kernel, dim3(sc->B), dim3(256), 0, st, A, (const int32_t*)w.sel, (const double*)w.sums, d_loss, d_traj,
                            d_tgt);

@@ -104,6 +104,25 @@ def _compact_or_zero(pen, mask):
     return v
 
 
+def _set_lazy_terms(out, keys, forward_terms, *args, **kwargs):
+    """The logging entries ``keys`` of a fused loss call's dict: ``forward_terms(*args, **kwargs)`` runs once, when the first of them
+    is read, and fills them all.  It runs on the SNAPSHOT of the closure's inputs that the caller passes (the optimiser updates z in
+    place afterwards) and without building a second autograd graph: 'loss' is the differentiable entry."""
+    terms = {}
+
+    def term(key):
+        def thunk():
+            if not terms:
+                with torch.no_grad():
+                    ft = forward_terms(*args, **kwargs)
+                    for k in list(ft.keys()):
+                        terms[k] = ft[k]          # (resolves the lazy lists of that dict)
+            return terms[key]
+        return thunk
+    for key in keys:
+        out.set_lazy(key, term(key))
+
+
 def interp_traj(future_pred, scale_factor=3):
     """Linear up-sampling in time + heading renormalisation (reference :625-644)."""
     multi = future_pred.dim() == 4
@@ -346,26 +365,10 @@ class AvoidCollLoss(nn.Module):
         out = LossDict()
         loss, _ = ops.avoid_coll_loss(future_pred, z, prior_out[0], prior_out[1], self._setup())
         out['loss'] = loss
-        terms = {}
-
-        # the logging entries are evaluated on a snapshot of the closure's inputs (the optimiser updates z in place afterwards) and
-        # without building a second autograd graph: 'loss' is the differentiable entry
-        fp_s, z_s = future_pred.detach(), z.detach().clone()
-
-        def term(key):
-            def thunk():
-                if not terms:
-                    with torch.no_grad():
-                        ft = self.forward_terms(fp_s, z_s, prior_out)
-                        for k in list(ft.keys()):
-                            terms[k] = ft[k]          # (resolves the lazy lists of that dict)
-                return terms[key]
-            return thunk
         w = self.loss_weights
-        for key, wk in (('coll_veh_loss', 'coll_veh'), ('coll_env_loss', 'coll_env'), ('motion_prior_loss', 'motion_prior'),
-                        ('init_loss', 'init_z')):
-            if w[wk] > 0.0:
-                out.set_lazy(key, term(key))
+        _set_lazy_terms(out, [key for key, wk in (('coll_veh_loss', 'coll_veh'), ('coll_env_loss', 'coll_env'),
+                                                  ('motion_prior_loss', 'motion_prior'), ('init_loss', 'init_z')) if w[wk] > 0.0],
+                        self.forward_terms, future_pred.detach(), z.detach().clone(), prior_out)
         return out
 
     def forward_terms(self, future_pred, z, prior_out):
@@ -485,25 +488,11 @@ class AdvGenLoss(nn.Module):
         loss, _, soft, _ = ops.adv_gen_loss(future_pred, tgt_traj, z, prior_out[0], prior_out[1], self._setup(),
                                             attack_agt_idx=attack_agt_idx, scene_alive=scene_alive)
         out = LossDict()
-        terms = {}
-
-        fp_s, tg_s, z_s = future_pred.detach(), tgt_traj.detach(), z.detach().clone()      # snapshot: see AvoidCollLoss.forward
-        alive_s = None if scene_alive is None else scene_alive.clone()
-
-        def term(key):
-            def thunk():
-                if not terms:
-                    with torch.no_grad():
-                        ft = self.forward_terms(fp_s, tg_s, z_s, prior_out, attack_agt_idx=attack_agt_idx, scene_alive=alive_s)
-                        for k in list(ft.keys()):
-                            terms[k] = ft[k]
-                return terms[key]
-            return thunk
-        for key, present in (('init_loss', w.get('init_z', 0.0) > 0.0), ('motion_prior_loss', w.get('motion_prior', 0.0) > 0.0),
-                             ('coll_veh_loss', w.get('coll_veh', 0.0) > 0.0), ('coll_veh_plan_loss', w.get('coll_veh_plan', 0.0) > 0.0),
-                             ('coll_env_loss', w.get('coll_env', 0.0) > 0.0), ('adv_crash_loss', True)):
-            if present:
-                out.set_lazy(key, term(key))
+        _set_lazy_terms(out, [key for key, wk in (('init_loss', 'init_z'), ('motion_prior_loss', 'motion_prior'), ('coll_veh_loss', 'coll_veh'),
+                                                  ('coll_veh_plan_loss', 'coll_veh_plan'), ('coll_env_loss', 'coll_env'))
+                              if w.get(wk, 0.0) > 0.0] + ['adv_crash_loss'],
+                        self.forward_terms, future_pred.detach(), tgt_traj.detach(), z.detach().clone(), prior_out,
+                        attack_agt_idx=attack_agt_idx, scene_alive=None if scene_alive is None else scene_alive.clone())
         out['loss'] = loss
         if return_mins:
             NT = future_pred.size(1) - self.crash_min_t

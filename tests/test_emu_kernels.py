@@ -696,6 +696,92 @@ def test_fused_losses_ragged_scenes(emu, monkeypatch):
     assert_close(res[1][3], res[0][3], 1e-4, 1e-7, 'adv d z')
 
 
+def _g5_loss_case(T):
+    g = golden('g5_losses.npz')
+    batch, map_idx, raster, dx = mg.g5_inputs(None, None)
+    state_n = Normalizer(*[t.double() for t in __import__('strive_amd.constants', fromlist=['x']).state_norm_tensors()])
+    att_n = Normalizer(*[t.double() for t in __import__('strive_amd.constants', fromlist=['x']).att_norm_tensors()])
+    traj = state_n.unnormalize(torch.from_numpy(g['adv_pred']).double())[:, :T, :4].float().contiguous()
+    return batch, map_idx, synth.SyntheticMapEnv(raster, dx), traj, att_n.unnormalize(batch.lw.double()).float()
+
+
+# (AvoidCollLoss, AdvGenLoss) workspace bytes at T = 4, scale = 3
+WS_BYTES = {'g5': (60672, 127744), 'one_and_three': (52992, 120320)}
+
+
+@pytest.mark.parametrize('case', sorted(WS_BYTES))
+def test_fused_loss_workspace_sizes_are_pinned(emu, case, monkeypatch):
+    """strive_avoid_coll_workspace_bytes / strive_adv_gen_workspace_bytes at two small shapes (the g5 batch; scenes of 1 and 3
+    agents, where the one-agent scene has no non-ego row and no pair besides itself), T = 4, scale = 3.  The expected values were
+    taken from the library as it was BEFORE each workspace's layout became one function that both measures and carves (then: a
+    byte formula and a carving sequence kept in step by hand): the sizes are ABI, callers may cache them.  Forward and backward then
+    run on a NaN-poisoned workspace of which they are given exactly that many bytes: carving must fit what the query reports (an
+    arena that runs out hands the kernels null pointers), and nothing may be written behind it."""
+    from strive_amd import ops
+    from strive_amd.losses.adv_gen_nusc import AvoidCollLoss, AdvGenLoss
+    monkeypatch.setattr(ops, '_lib_for', lambda *tensors: emu)
+    monkeypatch.setattr(ops, '_ws_cache', {})
+    T, D = 4, 32
+    if case == 'g5':
+        batch, map_idx, env, traj, veh_att = _g5_loss_case(T)
+    else:
+        batch, map_idx, env, traj, veh_att = _loss_case([1, 3], 'emu/ws_sizes')
+        traj = traj[:, :T].contiguous()
+    NA, B = traj.shape[0], batch.ptr.shape[0] - 1
+    ego = torch.zeros((NA,), dtype=torch.bool)
+    ego[batch.ptr[:-1]] = True
+    tgt = traj[ego].clone()
+    tgt[:, :, :2] += 1.5
+    mapixes = map_idx[batch.batch]
+    dev = traj.device
+    pk = ops._map_pack(env, dev)
+    d_loss = torch.ones((1,), dtype=torch.float32)
+
+    def latents(n):
+        return [synth.f32(synth.counter_uniform((n, D), 'emu/ws_sizes/%s%d' % (k, n), lo, hi))
+                for k, lo, hi in (('z', -1.0, 1.0), ('m', -0.5, 0.5), ('v', 0.3, 2.0))]
+
+    def guarded(nbytes, tag):
+        ws = poisoned_workspace(ops)(dev, nbytes, tag)
+        assert ws.numel() > nbytes and bool((ws == 0xFF).all())
+        return ws
+
+    # AvoidCollLoss
+    z, mu, var = latents(NA)
+    h = AvoidCollLoss({'coll_veh': 1.5, 'coll_env': 0.7, 'motion_prior': 0.02, 'init_z': 0.3}, veh_att, mapixes, env, z * 0.5,
+                      veh_coll_buffer=0.3, ptr=batch.ptr)._setup()
+    st, _keep, nbytes = h.struct_for(T, NA, D, False)
+    assert nbytes == WS_BYTES[case][0], 'strive_avoid_coll_workspace_bytes: %d' % nbytes
+    ws = guarded(nbytes, 'avoid')
+    out, d_traj, d_z = torch.full((8,), float('nan')), torch.full_like(traj, float('nan')), torch.full_like(z, float('nan'))
+    emu.call('strive_avoid_coll_fwd', h.sc.ref(), pk.ref(), C.byref(st), L.ptr(traj), T, L.ptr(z), L.ptr(mu), L.ptr(var), L.ptr(out),
+             L.ptr(ws), nbytes, None)
+    emu.call('strive_avoid_coll_bwd', h.sc.ref(), C.byref(st), L.ptr(traj), T, L.ptr(z), L.ptr(mu), L.ptr(var), L.ptr(d_loss), L.ptr(ws),
+             nbytes, L.ptr(d_traj), L.ptr(d_z), None)
+    assert torch.isfinite(out).all() and torch.isfinite(d_traj).all() and torch.isfinite(d_z).all()
+    assert float(out[0]) > 0.0 and float(d_z.abs().max()) > 0.0
+    assert bool((ws[nbytes:] == 0xFF).all()), 'AvoidCollLoss wrote behind its workspace'
+
+    # AdvGenLoss
+    z, mu, var = latents(NA - B)
+    h = AdvGenLoss(mg.ADV_WEIGHTS, veh_att, mapixes, env, z * 0.5, batch.ptr, veh_coll_buffer=0.1, crash_loss_min_time=1,
+                   crash_loss_min_infront=-0.5)._setup()
+    st, _keep, nbytes = h.struct_for(T, D, None, None)
+    assert nbytes == WS_BYTES[case][1], 'strive_adv_gen_workspace_bytes: %d' % nbytes
+    ws = guarded(nbytes, 'adv')
+    nan = float('nan')
+    out, soft, rew = torch.full((16,), nan), torch.full((NA - B, T - 1), nan), torch.full((NA - B,), nan)
+    d_traj, d_tgt, d_z = torch.full_like(traj, nan), torch.full_like(tgt, nan), torch.full_like(z, nan)
+    emu.call('strive_adv_gen_fwd', h.sc.ref(), pk.ref(), C.byref(st), L.ptr(traj), L.ptr(tgt), T, L.ptr(z), L.ptr(mu), L.ptr(var),
+             L.ptr(out), L.ptr(soft), L.ptr(rew), L.ptr(ws), nbytes, None)
+    emu.call('strive_adv_gen_bwd', h.sc.ref(), C.byref(st), L.ptr(traj), L.ptr(tgt), T, L.ptr(z), L.ptr(mu), L.ptr(var), L.ptr(d_loss),
+             L.ptr(ws), nbytes, L.ptr(d_traj), L.ptr(d_tgt), L.ptr(d_z), None)
+    for name, t in (('out', out), ('soft', soft), ('rew', rew), ('d_traj', d_traj), ('d_tgt', d_tgt), ('d_z', d_z)):
+        assert torch.isfinite(t).all(), name
+    assert float(out[0]) > 0.0 and float(d_z.abs().max()) > 0.0 and float(d_tgt.abs().max()) > 0.0
+    assert bool((ws[nbytes:] == 0xFF).all()), 'AdvGenLoss wrote behind its workspace'
+
+
 def _adv_quarantine_case(dead, key='emu/quarantine', sizes=(3, 5, 2, 4), D=32):
     """a ragged batch, the same batch without the scenes in ``dead``, and the row maps between them"""
     batch, map_idx, env, traj, veh_att = _loss_case(list(sizes), key)
