@@ -808,6 +808,81 @@ int strive_bicycle_step(const StriveDecoder* dec, const float* state, const floa
 int strive_rel_pose(const float* frame, const float* poses, const float* g_out, float* out, float* g_frame, float* g_poses,
                     int32_t N, int32_t M, strive_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Scene dataset: the part of the reference's NuScenesDataset that follows the devkit (reference
+ * src/datasets/nuscenes_dataset.py:416-589 post_process, :594-704 __getitem__, plus the PyG DataLoader collation), on
+ * tables that stay on the device.  All scenes are flattened: a scene's agents are consecutive, the ego first; an agent's
+ * table rows are the frames of its scene's timeline.
+ * ---------------------------------------------------------------------------------------------- */
+
+/* The records compile_data hands to post_process (reference src/datasets/nuscenes_dataset.py:350-414), nothing derived. */
+typedef struct StriveTracks {
+    int32_t S, A, O;                  /* scenes, agents (egos included), observations */
+    const int32_t* frame_ptr;         /* (S+1) into ego_t */
+    const int64_t* ego_t;             /* microseconds: a scene's timeline */
+    const int32_t* agent_ptr;         /* (S+1); a scene's first agent is its ego */
+    const int32_t* scene_map;         /* (S) map index */
+    const int32_t* agent_scene;       /* (A) */
+    const int32_t* use;               /* (A) 0: the agent's category is not asked for (it is dropped) */
+    const double* lw;                 /* (A,2) length, width */
+    const int32_t* obs_ptr;           /* (A+1) */
+    const int32_t* obs_frame;         /* (O) index on the scene's timeline (ego_t_map, :435) */
+    const double* obs;                /* (O,5) x, y, h, hcos, hsin */
+} StriveTracks;
+
+/* scene2info of every scene (:463-571) as flat float64 tables; scenario scenes (compile_scenarios, :231-290) follow the
+ * track scenes in the same tables. */
+typedef struct StriveSceneTables {
+    int32_t S, A;
+    int64_t R;                        /* table rows: sum over agents of the frames of their scene */
+    const int32_t* agent_ptr;         /* (S+1) */
+    const int32_t* scene_T;           /* (S) frames */
+    const int32_t* scene_map;         /* (S) */
+    const int64_t* row_ptr;           /* (A) first row of each agent */
+    const int32_t* cat;               /* (A) column of the one-hot `sem`; the ego's is that of 'car' (:613) */
+    const double* lw;                 /* (A,2) */
+    double* traj;                     /* (R,6) x, y, hcos, hsin, s, hdot */
+    double* accel;                    /* (R,2) |d vel|, ddh */
+    int32_t* is_vis;                  /* (R) */
+    int32_t* kept;                    /* (A) 0: never on the drivable layer (:532-534) or not asked for */
+} StriveSceneTables;
+
+typedef struct StriveNorm {
+    float state_mean[6], state_std[6], att_mean[2], att_std[2];
+} StriveNorm;
+
+/* post_process for all agents of all track scenes in one launch (one workgroup per agent), float64, every operation
+ * rounded on its own.  Per observation of a non-ego agent: check_on_layer (reference src/datasets/nuscenes_utils.py:266-298
+ * with gen_car_coords :205-232) on raster layer 0 and, with carpark_layer > 0 (a raster that has a car-park layer), on that layer: grid L = rint(l / mdx),
+ * W = rint(w / mdx) (mdx = mean of all dx), torch.linspace(-1, 1, n) in fp32 widened (lin holds the tables of n = 0..nmax
+ * back to back, table n at lin_off[n]), scaled by l/2 and w/2, rotated, translated, divided by the map's dx, rounded half
+ * to even, outside pixels read pixel (0,0); a frame is kept if drivable >= 0.3 and carpark < 0.3 (fractions in fp32,
+ * :513-522).  Kept observations are scattered on the scene timeline (:524-530); velocity and heading_change_rate
+ * (nuscenes_utils.py:134-199: backward differences, forward at frame 0 and at a frame that follows a NaN unless it is the
+ * last) give s, |d vel|, hdot, ddh; frames with NaN speed lose their position (:545-551).  The ego takes the same
+ * arithmetic without the filter (:433-453).  Writes traj, accel, is_vis, kept of the first tr->A agents of tb.
+ * ws: tb->R * 8 doubles. */
+int strive_dataset_post_process(const StriveTracks* tr, const StriveMap* map, const StriveSceneTables* tb, int32_t carpark_layer,
+                                double mdx, const int32_t* lin_off, const float* lin, int32_t nmax, void* ws, size_t ws_bytes,
+                                strive_stream_t stream);
+
+/* seq (N,2) = (scene, first frame) of every window; counts[i] = agents __getitem__ would return for window i (:630-649):
+ * the ego, and every kept agent without a NaN in traj[midx-1] and, with require_full_past, in traj[:midx]. */
+int strive_dataset_window_counts(const StriveSceneTables* tb, const int32_t* seq, int32_t N, int32_t npast, int32_t nfuture,
+                                 int32_t require_full_past, int32_t* counts, strive_stream_t stream);
+
+/* __getitem__ (:594-704) and the DataLoader collation of B windows in one launch, one workgroup per window.
+ * meta (3, B+1) int64 from the host, which knows the counts: window indices, node offsets `ptr`, edge offsets.  The
+ * selected agents are compacted in table order (ego first); float64 -> fp32, then (x - mean) / std in fp32 (:651-663).
+ * past, past_gt (NA,PT,6), future, future_gt (NA,FT,6), lw (NA,2), sem (NA,NC), past_vis (NA,PT), future_vis (NA,FT) fp32;
+ * batch (NA), map_idx (B), edge_index (2,E) int64: per window the source-major clique without self loops (:678-687),
+ * offset by its first node. */
+int strive_dataset_gather_batch(const StriveSceneTables* tb, const int32_t* seq, const int64_t* meta, int32_t B, int32_t npast,
+                                int32_t nfuture, int32_t NC, int32_t require_full_past, const StriveNorm* norm, float* past,
+                                float* past_gt, float* future, float* future_gt, float* lw, float* sem, float* past_vis,
+                                float* future_vis, int64_t* batch, int64_t* map_idx, int64_t* edge_index, int64_t E,
+                                strive_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -128,6 +128,22 @@ class StrivePlanner(C.Structure):
                 ('ptr', C.c_void_p), ('scene_map', C.c_void_p), ('init', C.c_void_p), ('row_obj', C.c_void_p), ('row_scene', C.c_void_p)]
 
 
+class StriveTracks(C.Structure):
+    _fields_ = [('S', C.c_int32), ('A', C.c_int32), ('O', C.c_int32), ('frame_ptr', C.c_void_p), ('ego_t', C.c_void_p),
+                ('agent_ptr', C.c_void_p), ('scene_map', C.c_void_p), ('agent_scene', C.c_void_p), ('use', C.c_void_p), ('lw', C.c_void_p),
+                ('obs_ptr', C.c_void_p), ('obs_frame', C.c_void_p), ('obs', C.c_void_p)]
+
+
+class StriveSceneTables(C.Structure):
+    _fields_ = [('S', C.c_int32), ('A', C.c_int32), ('R', C.c_int64), ('agent_ptr', C.c_void_p), ('scene_T', C.c_void_p),
+                ('scene_map', C.c_void_p), ('row_ptr', C.c_void_p), ('cat', C.c_void_p), ('lw', C.c_void_p), ('traj', C.c_void_p),
+                ('accel', C.c_void_p), ('is_vis', C.c_void_p), ('kept', C.c_void_p)]
+
+
+class StriveNorm(C.Structure):
+    _fields_ = [('state_mean', C.c_float * 6), ('state_std', C.c_float * 6), ('att_mean', C.c_float * 2), ('att_std', C.c_float * 2)]
+
+
 P = C.c_void_p
 I = C.c_int32
 SZ = C.c_size_t
@@ -213,6 +229,11 @@ PROTOTYPES = {
     'strive_planner_workspace_bytes': (SZ, [C.POINTER(StrivePlanner), I, I]),
     'strive_planner_rollout': (C.c_int, [C.POINTER(StrivePlanner), P, P, I, P, I, P, I, I, P, P, P, P, SZ, P]),
     'strive_planner_routes': (C.c_int, [C.POINTER(StrivePlanner), I, P, I, I, P, P, P, P, P]),
+    'strive_dataset_post_process': (C.c_int, [C.POINTER(StriveTracks), C.POINTER(StriveMap), C.POINTER(StriveSceneTables), I, C.c_double,
+                                              P, P, I, P, SZ, P]),
+    'strive_dataset_window_counts': (C.c_int, [C.POINTER(StriveSceneTables), P, I, I, I, I, P, P]),
+    'strive_dataset_gather_batch': (C.c_int, [C.POINTER(StriveSceneTables), P, P, I, I, I, I, I, C.POINTER(StriveNorm), P, P, P, P, P, P,
+                                              P, P, P, P, P, C.c_int64, P]),
 }
 
 

@@ -12,6 +12,37 @@ class _RawEnv(object):
         self.nusc_raster, self.nusc_dx, self.bounds, self.L, self.W = maps, dx, list(bounds), L, W
 
 
+def angle_diff(theta1, theta2):
+    """Difference of two angle arrays folded into [-pi, pi) (reference :134-143), numpy in the arrays' own type: shifted by half
+    a turn, reduced with the floored modulo, shifted back; what still exceeds pi loses a turn."""
+    half_turn, turn = np.pi, 2 * np.pi
+    folded = np.mod(theta1 - theta2 + half_turn, turn) - half_turn
+    return np.where(folded > half_turn, folded - turn, folded)
+
+
+def _lead_filled(diff, isnan):
+    """Backward differences ``diff`` (one per frame pair) on the frames: frame 0 and every frame that follows a NaN frame take
+    the forward difference instead -- except the last frame, which keeps its backward one (reference :155-171, :183-198)."""
+    T = isnan.shape[0]
+    k = np.maximum(np.arange(T) - 1, 0)
+    lead = np.zeros((T,), dtype=bool)
+    lead[1:] = isnan[:-1] & ~isnan[1:]
+    lead[T - 1] = False
+    k[lead] = np.arange(T)[lead]
+    return diff[k]
+
+
+def heading_change_rate(h, t):
+    """(T) heading rates of angles that may be NaN (reference :145-171); host numpy, used for scenario files only -- the
+    track records go through the HIP post-processing kernel, which restates the same rule."""
+    return _lead_filled(angle_diff(h[1:], h[:-1]) / (t[1:] - t[:-1]), np.isnan(h))
+
+
+def velocity(pos, t):
+    """(T,D) velocities of positions that may be NaN (reference :173-199); host numpy, see heading_change_rate."""
+    return _lead_filled((pos[1:, :] - pos[:-1, :]) / (t[1:] - t[:-1]).reshape((-1, 1)), np.isnan(np.sum(pos, axis=1)))
+
+
 def gen_car_coords(xys, hs, C, L, W, bounds=None, ls=None, ws=None):
     """World coordinates (B,C,L,W,2) of a grid attached to each car (reference :205-232); torch glue."""
     B = hs.size(0)

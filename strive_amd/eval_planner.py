@@ -253,6 +253,7 @@ def get_parser():
     p.add_argument('--out', type=str, default='./out/eval_planner_out', help='output directory')
     p.add_argument('--scenario_dir', type=str, default=None, help='directory of scenario JSON files to evaluate on')
     p.add_argument('--skip_regular', action='store_true', help='only evaluate the scenarios of --scenario_dir')
+    p.add_argument('--tracks', type=str, default=None, help='tracks file (datasets/tracks.py) whose windows are the regular scenes')
     p.add_argument('--eval_replay_planner', action='store_true', help='evaluate the recorded ego trajectory instead of the planner')
     p.add_argument('--batch_scenes', type=int, default=64, help='scenes per planner / metrics call')
     p.add_argument('--lane_world', type=str, default=None, choices=['synthetic'], help='map environment with lane graphs')
@@ -273,16 +274,27 @@ def main(argv=None):
     if cfg['lane_world'] is None:
         raise SystemExit('eval_planner: the nuScenes devkit and data are not available here; a map environment with lane graphs must '
                          'be supplied from Python (run_planner_eval(plan_cfg, loader, map_env, ...)), or use --lane_world synthetic')
-    if not cfg['skip_regular']:
+    if not cfg['skip_regular'] and cfg['tracks'] is None:
         raise SystemExit('eval_planner: regular scenes need a dataset, which must be supplied from Python (run_planner_eval); '
-                         'pass --skip_regular to evaluate --scenario_dir alone')
+                         'pass --tracks FILE, or --skip_regular to evaluate --scenario_dir alone')
     plan_cfg_dict = {k: cfg['planner_' + k] for k in DEF_CONFIG}
     os.makedirs(cfg['out'], exist_ok=True)
     with open(os.path.join(cfg['out'], 'plan_cfg.json'), 'w') as f:
         json.dump(plan_cfg_dict, f)
-    run_planner_eval(PlannerConfig(**plan_cfg_dict), None, SyntheticLaneWorld(), cfg['dt'], cfg['device'], cfg['out'], None, None,
-                     scenario_dir=cfg['scenario_dir'], skip_regular=True, eval_replay_planner=cfg['eval_replay_planner'],
-                     batch_scenes=cfg['batch_scenes'])
+    if cfg['skip_regular'] or cfg['tracks'] is None:
+        run_planner_eval(PlannerConfig(**plan_cfg_dict), None, SyntheticLaneWorld(), cfg['dt'], cfg['device'], cfg['out'], None, None,
+                         scenario_dir=cfg['scenario_dir'], skip_regular=True, eval_replay_planner=cfg['eval_replay_planner'],
+                         batch_scenes=cfg['batch_scenes'])
+        return
+    # regular scenes: every window of the tracks file, one scene per item as the reference's loader of batch size 1 yields them
+    from . import synth
+    from .datasets.nuscenes_dataset import NuScenesDataset
+    raster, dx = synth.make_raster(M=MAX_MAPS_PER_CALL)
+    world = synth.SyntheticMapEnv(raster, dx, lane_graph=synth.make_lane_graph()).to(cfg['device'])
+    ds = NuScenesDataset(cfg['tracks'], world, device=cfg['device'])
+    run_planner_eval(PlannerConfig(**plan_cfg_dict), ds.loader(1), world, cfg['dt'], cfg['device'], cfg['out'], ds.get_state_normalizer(),
+                     ds.get_att_normalizer(), scenario_dir=cfg['scenario_dir'], skip_regular=False,
+                     eval_replay_planner=cfg['eval_replay_planner'], batch_scenes=cfg['batch_scenes'])
 
 
 if __name__ == '__main__':

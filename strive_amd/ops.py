@@ -296,16 +296,18 @@ def scene_info(scene_graph):
     return info
 
 
-def prime_scene_info(scene_graph, ptr_cpu, ei_cpu=None):
+def prime_scene_info(scene_graph, ptr_cpu, ei_cpu=None, clique_by_construction=False):
     """``scene_info`` for a graph whose tensors have just been copied to the device, from the HOST copies of its ``ptr`` and
     ``edge_index``: the same validation and the same SceneInfo, without reading the structure back from the device (which is a
-    host synchronisation per fresh batch).  The caller vouches that ``ptr_cpu`` / ``ei_cpu`` hold what ``scene_graph`` holds."""
+    host synchronisation per fresh batch).  The caller vouches that ``ptr_cpu`` / ``ei_cpu`` hold what ``scene_graph`` holds.
+    ``clique_by_construction``: the graph's ``edge_index`` was written on the device by strive_dataset_gather_batch from this very
+    ``ptr_cpu``, which builds nothing but the per-scene clique: there is no host copy to validate."""
     info = SceneInfo(ptr_cpu, scene_graph.past.device)
     ei = scene_graph.edge_index if 'edge_index' in scene_graph else None
     ptr = scene_graph.ptr
     info.ei_sig = None if ei is None else (ei.data_ptr(), ei._version, tuple(ei.shape))
     info.ptr_sig = (ptr.data_ptr(), ptr._version, tuple(ptr.shape))
-    if ei is not None:
+    if ei is not None and not clique_by_construction:
         if ei_cpu is None:
             raise ValueError('prime_scene_info needs the host copy of edge_index')
         exp = _expected_clique_keys(ptr_cpu, info.NA)

@@ -184,6 +184,96 @@ def make_batch(sizes, key='scene', PT=4, FT=12, NC=2, map_extent=(256.0, 256.0),
 
 
 # --------------------------------------------------------------------------------------------
+# track records (the scene dataset's input, datasets/tracks.py)
+# --------------------------------------------------------------------------------------------
+
+CARPARK_RECT = (60.0, 2.0, 72.0, 8.0)        # x0, y0, x1, y1 in metres: where add_carpark_layer marks a car park on every map
+TRACK_PATTERNS = ('full', 'late', 'gap', 'single', 'offroad_gap', 'never_on_road', 'carpark', 'wrap')
+
+
+def add_carpark_layer(raster, dx, layer=1):
+    """A copy of ``raster`` whose layer ``layer`` holds one car park (CARPARK_RECT) per map; returns (raster, layer_map)."""
+    out = raster.clone()
+    out[:, layer] = 0
+    for m in range(raster.shape[0]):
+        x0, y0, x1, y1 = CARPARK_RECT
+        out[m, layer, int(round(y0 / float(dx[m, 1]))):int(round(y1 / float(dx[m, 1]))) + 1,
+            int(round(x0 / float(dx[m, 0]))):int(round(x1 / float(dx[m, 0]))) + 1] = 1
+    return out, {'drivable_area': 0, 'road_segment': 0, 'lane': 0, 'carpark_area': layer}
+
+
+def _road_band_y(m, k, dx=0.25):
+    """Metres: (lower edge, upper edge) of the k-th horizontal road of map m of make_raster, and the centre of the block above it."""
+    period, road_w, off = 160 + 24 * m, 72 + 8 * m, 37 * m
+    dy = dx * (1.0 - 0.00007 * m)
+    lo = (k * period - off) * dy
+    return max(lo, 0.0), (k * period - off + road_w) * dy, (k * period - off + road_w + 0.5 * (period - road_w)) * dy
+
+
+def _block_x(m, k, dx=0.25):
+    """Metres: centre of the k-th gap between the vertical roads of map m of make_raster."""
+    period, road_w, off = 160 + 24 * m, 72 + 8 * m, 37 * m
+    return (k * period - 2 * off + road_w + 0.5 * (period - road_w)) * dx * (1.0 + 0.00013 * m)
+
+
+def make_tracks(n_scenes=4, n_agents=16, T=40, M=1, key='tracks', categories=('car', 'truck')):
+    """A deterministic tracks dict (datasets/tracks.py) on the world of ``make_raster(M=M)``: scene s lies on map s % M, its ego
+    drives along the first road, agent j follows TRACK_PATTERNS[j % 8] -- seen in every frame, first seen mid-scene, unobserved for a
+    few frames, seen in a single frame, off the road for a few frames, never on the road (the dataset drops it), standing on
+    CARPARK_RECT (dropped where the raster has ``add_carpark_layer``'s layer), heading oscillating across +-pi.  Timestamps jitter
+    around 2 Hz."""
+    tr = {'scene_name': [], 'scene_map': [], 'categories': list(categories), 'frame_ptr': [0], 'ego_t': [], 'agent_ptr': [0], 'lw': [],
+          'cat': [], 'obs_ptr': [0], 'obs_frame': [], 'obs': []}
+    for s in range(n_scenes):
+        m = s % M
+        k = '%s/%d' % (key, s)
+        tr['scene_name'].append('scene-%04d' % s)
+        tr['scene_map'].append('synthetic-%d' % m)
+        jit = np.rint(counter_uniform((T,), k + '/jit', -20000.0, 20000.0)).astype(np.int64)
+        tr['ego_t'].extend((1532402927000000 + 20000000 * s + 500000 * np.arange(T, dtype=np.int64) + jit).tolist())
+        tr['frame_ptr'].append(len(tr['ego_t']))
+        lo, hi, off_y = _road_band_y(m, 1 if m else 0)
+        off_x = _block_x(m, 1)
+        frames = np.arange(T)
+        for j in range(n_agents + 1):                               # j = 0: the ego
+            pat = 'full' if j == 0 else TRACK_PATTERNS[(j - 1) % len(TRACK_PATTERNS)]
+            lane_y = lo + 2.0 + (hi - lo - 4.0) * ((j * 5) % 7) / 6.0
+            x0 = 24.0 + 5.5 * (j % 23) + 0.37 * (j // 23)
+            v = 1.0 + 0.5 * (j % 5)
+            back = pat == 'wrap' or j % 3 == 2
+            x = x0 + (-1.0 if back else 1.0) * v * 0.5 * frames + (60.0 if back else 0.0)
+            y = np.full((T,), lane_y) + 0.05 * np.sin(0.4 * frames + j)
+            h = 0.03 * np.sin(0.7 * frames + j) + (math.pi if back else 0.0)
+            seen = np.ones((T,), dtype=bool)
+            if pat == 'late':
+                seen[:T // 3] = False
+            elif pat == 'gap':
+                seen[T // 2:T // 2 + 3] = False
+            elif pat == 'single':
+                seen[:] = False
+                seen[T // 4] = True
+            elif pat == 'offroad_gap':
+                x[T // 2:T // 2 + 2], y[T // 2:T // 2 + 2] = off_x, off_y
+            elif pat == 'never_on_road':
+                x, y = off_x + 0.1 * frames, np.full((T,), off_y)
+            elif pat == 'carpark':
+                x = 0.5 * (CARPARK_RECT[0] + CARPARK_RECT[2]) + 0.05 * frames
+                y = np.full((T,), 0.5 * (CARPARK_RECT[1] + CARPARK_RECT[3]))
+            h = (h + math.pi) % (2.0 * math.pi) - math.pi           # compile_data's arctan2 range
+            tr['lw'].append([4.084, 1.73] if j == 0 else [4.0 + 0.125 * (j % 9), 1.75 + 0.0625 * (j % 5)])
+            tr['cat'].append(0 if j == 0 else (j % len(categories)))
+            for t in frames[seen]:
+                tr['obs_frame'].append(int(t))
+                tr['obs'].append([x[t], y[t], h[t], math.cos(h[t]), math.sin(h[t])])
+            tr['obs_ptr'].append(len(tr['obs']))
+        tr['agent_ptr'].append(len(tr['lw']))
+    tr['lw'] = np.asarray(tr['lw'], dtype=np.float64)
+    tr['obs'] = np.asarray(tr['obs'], dtype=np.float64)
+    from .datasets.tracks import check_tracks
+    return check_tracks(tr)
+
+
+# --------------------------------------------------------------------------------------------
 # weights
 # --------------------------------------------------------------------------------------------
 
