@@ -71,6 +71,14 @@ struct StriveArena {
     }
     bool ok() const { return off <= cap; }
 };
+// Bytes a layout function takes: it runs over an arena without memory and without limit, whose offset is then the size.  The same
+// function over the caller's pointer carves, so a buffer's size query and its carving cannot drift apart.
+template <typename Layout>
+static inline size_t strive_measure(Layout&& layout) {
+    StriveArena ar(nullptr, SIZE_MAX);
+    layout(ar);
+    return ar.off;
+}
 
 // ---- wave-level reductions (64 lanes) ----
 // __shfl_xor compiles to ds_bpermute_b32: an LDS-crossbar round trip (~100 cycles) per step, six dependent steps per
@@ -87,11 +95,24 @@ template <int CTRL>
 __device__ __forceinline__ float dpp_move(float v) {
     return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, true));
 }
-__device__ __forceinline__ float wave_sum(float v) {
+// the four in-row steps alone: every lane gets the total / maximum of its row of 16 lanes (the scene kernels work on four rows
+// per wave instruction, lane = 16 * sub + q)
+__device__ __forceinline__ float row16_sum(float v) {
     v += dpp_move<STRIVE_DPP_QUAD_XOR1>(v);
     v += dpp_move<STRIVE_DPP_QUAD_XOR2>(v);
     v += dpp_move<STRIVE_DPP_ROW_HALF_MIRROR>(v);
     v += dpp_move<STRIVE_DPP_ROW_MIRROR>(v);
+    return v;
+}
+__device__ __forceinline__ float row16_max(float v) {
+    v = fmaxf(v, dpp_move<STRIVE_DPP_QUAD_XOR1>(v));
+    v = fmaxf(v, dpp_move<STRIVE_DPP_QUAD_XOR2>(v));
+    v = fmaxf(v, dpp_move<STRIVE_DPP_ROW_HALF_MIRROR>(v));
+    v = fmaxf(v, dpp_move<STRIVE_DPP_ROW_MIRROR>(v));
+    return v;
+}
+__device__ __forceinline__ float wave_sum(float v) {
+    v = row16_sum(v);
     const float r0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 0));
     const float r1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 16));
     const float r2 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 32));
@@ -99,10 +120,7 @@ __device__ __forceinline__ float wave_sum(float v) {
     return (r0 + r1) + (r2 + r3);
 }
 __device__ __forceinline__ float wave_max(float v) {
-    v = fmaxf(v, dpp_move<STRIVE_DPP_QUAD_XOR1>(v));
-    v = fmaxf(v, dpp_move<STRIVE_DPP_QUAD_XOR2>(v));
-    v = fmaxf(v, dpp_move<STRIVE_DPP_ROW_HALF_MIRROR>(v));
-    v = fmaxf(v, dpp_move<STRIVE_DPP_ROW_MIRROR>(v));
+    v = row16_max(v);
     const float r0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 0));
     const float r1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 16));
     const float r2 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 32));

@@ -317,20 +317,11 @@ static __global__ __launch_bounds__(256) void node1_bwd_kernel(GNNDev g, GNNGrad
 
 static inline size_t node1_bwd_lds_bytes(int in_ld, int xs_ld) { return Node1Lds::bytes(in_ld, xs_ld) + (size_t)(4 * RB_NODE * HLD + RB_NODE * in_ld) * 4; }
 
-// workspace of the per-step backward buffers shared by the rollout sweep and the stand-alone network backward
+// workspace of the per-step backward buffers shared by the rollout sweep and the stand-alone network backward (the one layout:
+// measured with strive_measure, carved from the caller's arena)
 struct GnnBwdBuffers {
     float *dX, *dA, *dP, *gpos_tgt, *DE1, *DPJ;
 };
-
-static inline size_t gnn_bwd_buffers_bytes(size_t R, int D, int max_n) {
-    size_t b = 0;
-    b += 2 * strive_align_up(R * D * 4, 256);                          // dX, dA
-    b += strive_align_up(R * STRIVE_HID * 4, 256);                     // dP
-    b += strive_align_up(R * 4 * 4, 256);                              // gpos_tgt
-    b += strive_align_up(R * (size_t)max_n * STRIVE_HID * 4, 256);     // DE1
-    b += strive_align_up(R * (size_t)max_n * 4 * 4, 256);              // DPJ
-    return b;
-}
 
 static inline GnnBwdBuffers gnn_bwd_buffers_take(StriveArena& ar, size_t R, int D, int max_n) {
     GnnBwdBuffers w;

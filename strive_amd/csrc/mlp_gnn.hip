@@ -170,7 +170,7 @@ extern "C" size_t strive_gnn_bwd_workspace_bytes(const StriveGNN* gnn, const Str
     const size_t R = (size_t)sc->NA * sc->NS;
     float* fake = reinterpret_cast<float*>(uintptr_t(1) << 20);      // (planning only: nothing is dereferenced)
     const size_t tape = gnn_bwd_plan(*gnn, *sc, fake, fake).tape_floats;
-    return strive_gnn_workspace_bytes(gnn, sc) + gnn_bwd_buffers_bytes(R, gnn->D, sc->max_n > 0 ? sc->max_n : 1) +
+    return strive_gnn_workspace_bytes(gnn, sc) + strive_measure([&](StriveArena& a) { gnn_bwd_buffers_take(a, R, gnn->D, sc->max_n > 0 ? sc->max_n : 1); }) +
            strive_align_up(R * 4 * 4, 256) + strive_align_up(sizeof(WJobTable), 256) + strive_align_up(tape * 4, 256) + 4096;
 }
 

@@ -10,7 +10,6 @@
 // (cheap: the GNN/GRU are ~1.6 MFLOP per agent-step against 300 MFLOP for the CNN, which needs no backward
 // at all because the reference crops at pos.detach()).  The backward is four launches per step:
 // node1 (recompute), gru_bwd, node2_bwd, edge_bwd, node1_bwd.
-#include <atomic>
 #include <type_traits>
 #include "gnn_bwd_kernels.h"
 
@@ -89,16 +88,19 @@ struct Tape {
     __host__ __device__ float* A_t(int t) const { return A + (size_t)t * R * 64; }
     __host__ __device__ float* loc_t(int t) const { return loc + (size_t)t * R * 4; }
     __host__ __device__ int32_t* ARG_t(int t) const { return ARG + (size_t)t * R * 64; }
+    // what the GNN kernels of step t write (forward) and read (reverse sweep): all of it lives in the tape
+    GnnBuffers gnn_t(int t) const {
+        GnnBuffers gb;
+        gb.X = X_t(t); gb.P = P_t(t); gb.Q = Q_t(t); gb.A = A_t(t); gb.ARG = ARG_t(t); gb.PRE_IN = PRE_IN_t(t); gb.PRE_E = PRE_E_t(t);
+        return gb;
+    }
 };
 
-static size_t tape_bytes_for(size_t R, int FT, int max_n) {
-    const size_t per = 64 + 64 + 4 + 8 + 192 + 64 + 4 + 64 + 64 + 2 * STRIVE_HID +
-                       2 * STRIVE_HID + (size_t)max_n * 2 * STRIVE_HID + STRIVE_HID + 2 * STRIVE_HID + 4 + 3 * 256;
-    return strive_align_up(R * FT * per * 4 + 17 * 256, 256);
-}
+// max_n of a batch as the layouts use it (an unset max_n sizes one source row per target)
+static inline int clamped_max_n(const StriveScenes& sc) { return sc.max_n > 0 ? sc.max_n : 1; }
 
-static Tape carve_tape(void* p, size_t bytes, size_t R, int FT, int max_n) {
-    StriveArena ar(p, bytes);
+// the tape's layout: measures (strive_measure) and carves
+static Tape tape_layout(StriveArena& ar, size_t R, int FT, int max_n) {
     Tape t;
     t.R = R;
     t.max_n = max_n;
@@ -120,6 +122,13 @@ static Tape carve_tape(void* p, size_t bytes, size_t R, int FT, int max_n) {
     t.DEC = ar.take<float>(R * FT * 4);
     t.GATES = ar.take<float>(R * FT * 3 * 256);
     return t;
+}
+
+// the caller's tape carved into `tp`; false: it is smaller than strive_rollout_tape_bytes reports
+static bool carve_tape(const StriveScenes& sc, int FT, const void* tape, size_t tape_bytes, Tape& tp) {
+    StriveArena ar(const_cast<void*>(tape), tape_bytes);
+    tp = tape_layout(ar, (size_t)sc.NA * sc.NS, FT, clamped_max_n(sc));
+    return ar.ok();
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -465,41 +474,44 @@ bool scene_form_prepare() {
 }
 
 int scene_kernels_prepare() {
-    static std::atomic<unsigned long long> done{0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev > 63) dev = 0;
-    if (done.load(std::memory_order_acquire) & (1ull << dev)) return 0;
+    static PerDeviceOnce once;
+    const int dev = once.device();
+    if (once.is_done(dev)) return 0;
     if (scene_form_prepare<6, STRIVE_ZDIM>() || scene_form_prepare<5, 0>() || scene_form_prepare<6, 0>() || scene_form_prepare<7, 0>()) {
         strive_set_error("rollout: the scene kernels' LDS request was refused");
         return -1;
     }
-    done.fetch_or(1ull << dev, std::memory_order_release);
+    once.set_done(dev);
     return 0;
 }
 
+// The forward's workspace (x, P, Q, A, ARG and the kept pre-activations of a step live in the tape).
+// part_a / part_arg: the two partial-maxima arrays the scene kernels' K-workgroup edge walk writes, (B, K <= 4, NR, 64) each, and
+// empty when the batch can never run on the scene kernels (multi-sample, > 16 agents per scene, weights without fragments).  Sized
+// from what the batch supports, not from the options of the moment, so that an option set between the size query and the call
+// cannot outgrow the workspace.
 struct FwdWs {
-    GnnBuffers gb;       // X, P, Q (A/ARG live in the tape)
+    unsigned long long* prof;      // option scene_prof (tools/scene_phase_probe.py): 64 phase counters at the start of the workspace
     int32_t* mapix_rows;
     void* cnn_ws;
     size_t cnn_bytes;
+    float* part_a;
+    int32_t* part_arg;
 };
 
-// elements of each of the two partial-maxima arrays the scene kernels' K-workgroup edge walk writes: (B, K <= 4, NR, 64), and none
-// when the batch can never run on the scene kernels (multi-sample, > 16 agents per scene, weights without fragments).  Sized from
-// what the batch supports, not from the options of the moment, so that an option set between the size query and the call cannot
-// outgrow the workspace.
-size_t fwd_part_elems(const StriveDecoder* dec, const StriveScenes* sc) {
-    return dec && sc && scn::supported(*dec, *sc) ? (size_t)sc->B * 4 * scn::NR * 64 : 0;
-}
-
-size_t fwd_ws_bytes(size_t R, size_t part_elems) {
-    size_t b = 0;
-    b += strive_align_up(R * 64 * 4, 256);
-    b += 2 * strive_align_up(R * STRIVE_HID * 4, 256);
-    b += strive_align_up(R * 4, 256);
-    b += strive_align_up(strive_map_cnn_workspace_bytes((int32_t)R), 256);
-    b += 2 * strive_align_up(part_elems * 4, 256);
-    return b;
+FwdWs fwd_ws_layout(StriveArena& ar, const StriveDecoder* dec, const StriveScenes& sc) {
+    const size_t R = (size_t)sc.NA * sc.NS, part_elems = dec && scn::supported(*dec, sc) ? (size_t)sc.B * 4 * scn::NR * 64 : 0;
+    FwdWs w;
+    // R x 1280 bytes: once x, P and Q of one step, which no kernel was ever given (every step's live in the tape).  The bytes stay:
+    // the map CNN's workspace behind them keeps its offset (without them the refine closure measured 0.05 ms slower, see
+    // profiles/r21_rollout_host_refactor.md), and their first 512 hold the phase counters of option scene_prof
+    w.prof = ar.take<unsigned long long>(R * (64 + 2 * STRIVE_HID) / 2);
+    w.mapix_rows = ar.take<int32_t>(R);
+    w.cnn_bytes = strive_map_cnn_workspace_bytes((int32_t)R);
+    w.cnn_ws = ar.take<char>(w.cnn_bytes);
+    w.part_a = ar.take<float>(part_elems);
+    w.part_arg = ar.take<int32_t>(part_elems);
+    return w;
 }
 
 DynParams dyn_params(const StriveDecoder& d) {
@@ -554,6 +566,34 @@ int check_decoder(const StriveDecoder* dec, const StriveScenes* sc, int FT) {
     return 0;
 }
 
+// the by-value kernel arguments every rollout kernel takes from the decoder pack
+struct DecoderDev { GNNDev gd; GRUDev gr; scn::GRUFrag gf; DynParams dp; };
+DecoderDev decoder_dev(const StriveDecoder& d) { return DecoderDev{gnn_dev(d.gnn), gru_dev(d.gru), scn::gru_frag(d.gru), dyn_params(d)}; }
+
+// the scene step's arguments that hold for a whole rollout; the step loop sets t, the launch sets mode
+scn::StepArgsS scene_step_args(const StriveDecoder& dec, const StriveScenes& sc, int FT, const float* sem, const float* lw, const float* z,
+                               const float* ext_future, float* traj, int KW, float* part_a, int32_t* part_arg) {
+    scn::StepArgsS a;
+    a.t = 0; a.FT = FT; a.NC = dec.gnn.NC; a.max_n = sc.max_n; a.mode = 0; a.sem = sem; a.lw = lw; a.z = z; a.ext = ext_future; a.ptr = sc.ptr;
+    a.par = dec.scene_par; a.traj = traj; a.KW = KW; a.part_a = part_a; a.part_arg = part_arg;
+    return a;
+}
+
+// one launch of scene_fwd_step_kernel; prof != null: the form that adds workgroup 0's phase ticks to those counters
+void launch_scene_step(const StriveDecoder& dec, const DecoderDev& dd, scn::StepArgsS a, int mode, dim3 grid, const Tape& tp,
+                       unsigned long long* prof, hipStream_t stream) {
+    a.mode = mode;
+    scene_form(dec, [&](auto kin, auto zfix) {
+        constexpr int KIN = decltype(kin)::value, ZFIX = decltype(zfix)::value;
+        if (prof)
+            hipLaunchKernelGGL((scn::scene_fwd_step_kernel<true, KIN, ZFIX>), grid, dim3(scn::NTHR), scn::FwdLds::BYTES, stream, dd.gd, dd.gr,
+                               dd.gf, dd.dp, a, tp, prof);
+        else
+            hipLaunchKernelGGL((scn::scene_fwd_step_kernel<false, KIN, ZFIX>), grid, dim3(scn::NTHR), scn::FwdLds::BYTES, stream, dd.gd, dd.gr,
+                               dd.gf, dd.dp, a, tp, prof);
+    });
+}
+
 }  // namespace
 
 extern "C" int strive_rollout_scene_resident(const StriveDecoder* dec, const StriveScenes* sc) {
@@ -563,7 +603,7 @@ extern "C" int strive_rollout_scene_resident(const StriveDecoder* dec, const Str
 
 extern "C" size_t strive_rollout_tape_bytes(const StriveDecoder* dec, const StriveScenes* sc, int32_t FT) {
     if (!sc) return 0;
-    return tape_bytes_for((size_t)sc->NA * sc->NS, FT, sc->max_n > 0 ? sc->max_n : 1);
+    return strive_measure([&](StriveArena& ar) { tape_layout(ar, (size_t)sc->NA * sc->NS, FT, clamped_max_n(*sc)); });
 }
 
 extern "C" size_t strive_rollout_keep_bytes(const StriveDecoder* dec, const StriveScenes* sc, int32_t FT) {
@@ -586,50 +626,58 @@ static int rollout_forward(const StriveDecoder* dec, const StriveScenes* sc, con
     STRIVE_CHECK_ARG(!(ext_future && sc->NS != 1), "ext_future with multiple samples is not supported");
     const size_t R = (size_t)sc->NA * sc->NS;
     if (R == 0) return 0;
-    STRIVE_CHECK_ARG(tape_bytes >= tape_bytes_for(R, FT, sc->max_n > 0 ? sc->max_n : 1), "tape too small");
+    Tape tp;
+    STRIVE_CHECK_ARG(carve_tape(*sc, FT, tape, tape_bytes, tp), "tape too small");
     STRIVE_CHECK_ARG(ws_bytes >= strive_rollout_workspace_bytes(dec, sc, FT), "workspace too small");
     hipStream_t stream = (hipStream_t)stream_;
-    Tape tp = carve_tape(tape, tape_bytes, R, FT, sc->max_n > 0 ? sc->max_n : 1);
     StriveArena ar(ws, ws_bytes);
-    FwdWs w;
-    w.gb.X = ar.take<float>(R * 64);
-    w.gb.P = ar.take<float>(R * STRIVE_HID);
-    w.gb.Q = ar.take<float>(R * STRIVE_HID);
-    w.mapix_rows = ar.take<int32_t>(R);
-    w.cnn_bytes = strive_map_cnn_workspace_bytes((int32_t)R);
-    w.cnn_ws = ar.take<char>(w.cnn_bytes);
-    const size_t part_n = fwd_part_elems(dec, sc);
-    float* part_a = ar.take<float>(part_n);
-    int32_t* part_arg = ar.take<int32_t>(part_n);
+    const FwdWs w = fwd_ws_layout(ar, dec, *sc);
     STRIVE_CHECK_ARG(ar.ok(), "workspace arena overflow");
 
-    const GNNDev gd = gnn_dev(dec->gnn);
-    const GRUDev gr = gru_dev(dec->gru);
-    const DynParams dp = dyn_params(*dec);
+    const DecoderDev dd = decoder_dev(*dec);
     const ScenesDev sd = scenes_dev(*sc);
     const int NC = dec->gnn.NC;
     const int in_ld1 = ld4(dec->gnn.mlp_in.dims[0]), xs_ld = ld4(64 + NC), in_ld2 = ld4(128 + NC);
     const int nb = (int)((R + RB_NODE - 1) / RB_NODE);
-
     const bool direct = decoder_direct(*dec);
+
+    // The plan of a step, picked once:
+    //   PHASE       node1 | edge | node2 kernels, one launch per phase
+    //   SCENE_ONE   the whole step of a scene in one launch of the scene kernel (mode 7)
+    //   SCENE_K     large scenes, round 5: K workgroups of the scene kernel per scene share the edge chunks (node phases repeated,
+    //               partial maxima folded by the second launch): mode 3 on (B, K) | mode 4
+    //   SCENE_EDGE  node phases on the scene kernel, the edge rows on one workgroup per target node in between (gnn_kernels.h):
+    //               mode 1 | gnn_edge_kernel | mode 4.  Large scenes in the round-4 form, grid B; and batches with scenes of more than
+    //               16 agents (round 6, option scene_tiles): the node phases per 16-row tile of a scene, grid (B, 1, tiles) -- matrix
+    //               tiles of 16 rows instead of 4-row blocks
+    enum { PHASE, SCENE_ONE, SCENE_K, SCENE_EDGE } plan = PHASE;
     const bool scene = scene_kernels_on(dec, sc);
     const bool scene_tiles = !scene && scene_tiles_on(dec, sc);
     if ((scene || scene_tiles) && scene_kernels_prepare()) return -1;
-    const scn::GRUFrag gf = scn::gru_frag(dec->gru);
-    const bool scene_prof = scene && strive_tuning().scene_prof != 0;
+    unsigned long long* prof = scene && strive_tuning().scene_prof != 0 ? w.prof : nullptr;
     // scenes of >= option scene_split agents (default 12 = three 64-row edge chunks; 0 = never): their 130-240 edge rows are 3-4
     // chunks on ONE CU inside the one-launch scene step.  Round 4 moved them to gnn_edge_kernel (one workgroup per target) from 15
-    // agents on (profiles/r04_ab_scene_split.txt); round 5 shares the chunks among K workgroups of the scene kernel itself (below):
+    // agents on (profiles/r04_ab_scene_split.txt); round 5 shares the chunks among K workgroups of the scene kernel itself:
     // a wash against the per-target kernel at 16 agents per scene, -2 % / -4 % of the refine closure at 14 / 12 agents where the
     // per-target kernel did not pay (profiles/r05_ab_fwd_k.json)
     const int split_min = strive_tuning().scene_split;
     const bool scene_split = scene && split_min > 0 && sc->max_n >= split_min;
     // option scene_fwd_k = workgroups per scene for the edge chunks of such scenes (default: one per chunk, <= 4; 0 = the round-4
-    // form: scene kernel | one workgroup per target in gnn_edge_kernel | scene kernel)
+    // form)
     int fwd_k = (sc->max_n * (sc->max_n - 1) + scn::EC - 1) / scn::EC;
     if (strive_tuning().scene_fwd_k >= 0) fwd_k = strive_tuning().scene_fwd_k;
     fwd_k = fwd_k > 4 ? 4 : fwd_k;
-    if (scene_prof) fwd_k = 0;
+    if (prof) fwd_k = 0;
+    dim3 grid((unsigned)sc->B);
+    if (scene) plan = !scene_split ? SCENE_ONE : (fwd_k > 0 ? SCENE_K : SCENE_EDGE);
+    else if (scene_tiles) {
+        plan = SCENE_EDGE;
+        grid = dim3((unsigned)sc->B, 1, (unsigned)((sc->max_n + scn::NR - 1) / scn::NR));
+    }
+    scn::StepArgsS sa = scene_step_args(*dec, *sc, FT, sem, lw, z, ext_future, traj, plan == SCENE_K ? fwd_k : 0,
+                                        scene ? w.part_a : nullptr, scene ? w.part_arg : nullptr);
+    auto scene_step = [&](int mode, dim3 g) { launch_scene_step(*dec, dd, sa, mode, g, tp, prof, stream); };
+
     hipLaunchKernelGGL(rollout_init_kernel, dim3((unsigned)((R * 64 + 255) / 256)), dim3(256), 0, stream, tp, past_last,
                        past_feat, map_feat, mapix, w.mapix_rows, (int)R, sc->NS);
     // map feature of step t + 1 at the pose step t produced (reference traffic_model.py:694-695)
@@ -642,89 +690,37 @@ static int rollout_forward(const StriveDecoder* dec, const StriveScenes* sc, con
                                   tp.mf_t(t + 1), w.cnn_ws, w.cnn_bytes, stream_);
     };
     for (int t = 0; t < FT; ++t) {
-        if (scene) {
-            scn::StepArgsS a;
-            a.t = t; a.FT = FT; a.NC = NC; a.max_n = sc->max_n; a.sem = sem; a.lw = lw; a.z = z; a.ext = ext_future; a.ptr = sc->ptr;
-            a.par = dec->scene_par; a.traj = traj; a.KW = 0; a.part_a = part_a; a.part_arg = part_arg;
-            auto launch_scene = [&](int mode, int ky = 1) {
-                a.mode = mode;
-                scene_form(*dec, [&](auto kin, auto zfix) {
-                    constexpr int KIN = decltype(kin)::value, ZFIX = decltype(zfix)::value;
-                    if (scene_prof)       // (tools/scene_phase_probe.py: phase ticks of workgroup 0 at the start of the workspace)
-                        hipLaunchKernelGGL((scn::scene_fwd_step_kernel<true, KIN, ZFIX>), dim3((unsigned)sc->B, (unsigned)ky), dim3(scn::NTHR),
-                                           scn::FwdLds::BYTES, stream, gd, gr, gf, dp, a, tp, (unsigned long long*)ws);
-                    else
-                        hipLaunchKernelGGL((scn::scene_fwd_step_kernel<false, KIN, ZFIX>), dim3((unsigned)sc->B, (unsigned)ky), dim3(scn::NTHR),
-                                           scn::FwdLds::BYTES, stream, gd, gr, gf, dp, a, tp, (unsigned long long*)nullptr);
-                });
-            };
-            if (scene_split && fwd_k > 0) {
-                // large scenes, round 5: K workgroups of the scene kernel per scene share the edge chunks (node phases repeated, partial
-                // maxima folded by the second launch): two launches per step instead of three, the 64-row chunk form for the edges
-                a.KW = fwd_k;
-                launch_scene(3, fwd_k);
-                launch_scene(4);
-                a.KW = 0;
-            } else if (scene_split) {
-                // large scenes: node phases per scene, the edge rows on one workgroup per target node in between (gnn_kernels.h)
-                GnnBuffers gb = w.gb;
-                gb.A = tp.A_t(t); gb.ARG = tp.ARG_t(t); gb.X = tp.X_t(t); gb.P = tp.P_t(t); gb.Q = tp.Q_t(t);
-                gb.PRE_IN = tp.PRE_IN_t(t); gb.PRE_E = tp.PRE_E_t(t);
-                launch_scene(1);
-                hipLaunchKernelGGL(gnn_edge_kernel, dim3((unsigned)R), dim3(256), EdgeLds::bytes(), stream, gd, sd, tp.pos_t(t), gb);
-                launch_scene(4);
-            } else {
-                launch_scene(7);
-            }
-            if (t < FT - 1) {
-                int rc = encode_step(t);
-                if (rc) return rc;
-            }
-            continue;
+        const GnnBuffers gb = tp.gnn_t(t);
+        auto edge_rows = [&] { hipLaunchKernelGGL(gnn_edge_kernel, dim3((unsigned)R), dim3(256), EdgeLds::bytes(), stream, dd.gd, sd, tp.pos_t(t), gb); };
+        sa.t = t;
+        switch (plan) {
+        case PHASE: {
+            FeatSrc f = decoder_features(tp, t, sem, z, lw, NC, decoder_zdim(*dec));
+            hipLaunchKernelGGL(gnn_node1_kernel, dim3(nb), dim3(256), Node1Lds::bytes(in_ld1, xs_ld), stream, dd.gd, sc->NS, f, sem,
+                               gb, (int)R);
+            edge_rows();
+            StepArgs a;
+            a.t = t; a.FT = FT; a.R = (int)R; a.NS = sc->NS; a.X = gb.X; a.sem = sem; a.lw = lw; a.ext = ext_future;
+            a.ptr = sc->ptr; a.scene_of = sc->scene_of; a.traj = traj;
+            if (direct)
+                hipLaunchKernelGGL(rollout_node2_kernel<true>, dim3(nb), dim3(256), node2r_lds_bytes(in_ld2), stream, dd.gd, dd.gr, dd.dp, a, tp);
+            else
+                hipLaunchKernelGGL(rollout_node2_kernel<false>, dim3(nb), dim3(256), node2r_lds_bytes(in_ld2), stream, dd.gd, dd.gr, dd.dp, a, tp);
+            break;
         }
-        GnnBuffers gb = w.gb;
-        gb.A = tp.A_t(t);
-        gb.ARG = tp.ARG_t(t);
-        gb.X = tp.X_t(t);
-        gb.P = tp.P_t(t);
-        gb.Q = tp.Q_t(t);
-        gb.PRE_IN = tp.PRE_IN_t(t);
-        gb.PRE_E = tp.PRE_E_t(t);
-        if (scene_tiles) {
-            // scenes of more than 16 agents: mlp_in .. P / Q and update MLP .. GRU .. dynamics per 16-row tile of a scene on the scene
-            // kernel (grid (B, 1, tiles): matrix tiles of 16 rows instead of 4-row blocks, one launch each), the edge rows in between
-            // on one workgroup per target node
-            scn::StepArgsS a;
-            a.t = t; a.FT = FT; a.NC = NC; a.max_n = sc->max_n; a.sem = sem; a.lw = lw; a.z = z; a.ext = ext_future; a.ptr = sc->ptr;
-            a.par = dec->scene_par; a.traj = traj; a.KW = 0; a.part_a = nullptr; a.part_arg = nullptr;
-            const dim3 grid((unsigned)sc->B, 1, (unsigned)((sc->max_n + scn::NR - 1) / scn::NR));
-            scene_form(*dec, [&](auto kin, auto zfix) {
-                constexpr int KIN = decltype(kin)::value, ZFIX = decltype(zfix)::value;
-                a.mode = 1;
-                hipLaunchKernelGGL((scn::scene_fwd_step_kernel<false, KIN, ZFIX>), grid, dim3(scn::NTHR), scn::FwdLds::BYTES, stream, gd, gr, gf, dp,
-                                   a, tp, (unsigned long long*)nullptr);
-                hipLaunchKernelGGL(gnn_edge_kernel, dim3((unsigned)R), dim3(256), EdgeLds::bytes(), stream, gd, sd, tp.pos_t(t), gb);
-                a.mode = 4;
-                hipLaunchKernelGGL((scn::scene_fwd_step_kernel<false, KIN, ZFIX>), grid, dim3(scn::NTHR), scn::FwdLds::BYTES, stream, gd, gr, gf, dp,
-                                   a, tp, (unsigned long long*)nullptr);
-            });
-            if (t < FT - 1) {
-                int rc = encode_step(t);
-                if (rc) return rc;
-            }
-            continue;
+        case SCENE_ONE:
+            scene_step(7, grid);
+            break;
+        case SCENE_K:
+            scene_step(3, dim3((unsigned)sc->B, (unsigned)fwd_k));
+            scene_step(4, grid);
+            break;
+        case SCENE_EDGE:
+            scene_step(1, grid);
+            edge_rows();
+            scene_step(4, grid);
+            break;
         }
-        FeatSrc f = decoder_features(tp, t, sem, z, lw, NC, decoder_zdim(*dec));
-        hipLaunchKernelGGL(gnn_node1_kernel, dim3(nb), dim3(256), Node1Lds::bytes(in_ld1, xs_ld), stream, gd, sc->NS, f, sem,
-                           gb, (int)R);
-        hipLaunchKernelGGL(gnn_edge_kernel, dim3((unsigned)R), dim3(256), EdgeLds::bytes(), stream, gd, sd, tp.pos_t(t), gb);
-        StepArgs a;
-        a.t = t; a.FT = FT; a.R = (int)R; a.NS = sc->NS; a.X = gb.X; a.sem = sem; a.lw = lw; a.ext = ext_future;
-        a.ptr = sc->ptr; a.scene_of = sc->scene_of; a.traj = traj;
-        if (direct)
-            hipLaunchKernelGGL(rollout_node2_kernel<true>, dim3(nb), dim3(256), node2r_lds_bytes(in_ld2), stream, gd, gr, dp, a, tp);
-        else
-            hipLaunchKernelGGL(rollout_node2_kernel<false>, dim3(nb), dim3(256), node2r_lds_bytes(in_ld2), stream, gd, gr, dp, a, tp);
         if (t < FT - 1) {
             int rc = encode_step(t);
             if (rc) return rc;
@@ -1026,14 +1022,37 @@ static size_t node2_bwd_lds_bytes(int in_ld) { return (Node2Lds::floats(in_ld) +
 // host orchestration: backward
 // =============================================================================================
 namespace {
-size_t bwd_ws_bytes(size_t R, int max_n) {
-    size_t b = 0;
-    b += strive_align_up(R * 8 * 4, 256);                  // g_state
-    b += 2 * strive_align_up(R * 4 * 4, 256);              // g_pos, d_loc
-    b += 2 * strive_align_up(R * 64 * 4, 256);             // g_pf, g_mf
-    b += strive_align_up(R * 192 * 4, 256);                // g_mem
-    b += gnn_bwd_buffers_bytes(R, 64, max_n);
-    return b;
+// the launch-per-phase sweep's workspace: the adjoint state carried from step to step and the per-step GNN buffers
+struct BwdWs {
+    float *g_state, *g_pos, *d_loc, *g_pf, *g_mem;
+    GnnBwdBuffers bw;
+};
+
+BwdWs bwd_ws_layout(StriveArena& ar, size_t R, int max_n) {
+    BwdWs w;
+    w.g_state = ar.take<float>(R * 8);
+    w.g_pos = ar.take<float>(R * 4);
+    w.d_loc = ar.take<float>(R * 4);
+    w.g_pf = ar.take<float>(R * 64);
+    ar.take<float>(R * 64);      // (was g_mf: the training path keeps the map-feature adjoints of every step in TrainOut::g_mf_all; the size is ABI)
+    w.g_mem = ar.take<float>(R * 192);
+    w.bw = gnn_bwd_buffers_take(ar, R, 64, max_n);
+    return w;
+}
+
+// The stepwise scene sweep's block in the workspace (scn::SweepArgs::part / state), 256 bytes in and with 256 bytes behind it; the
+// block is not part of strive_rollout_workspace_bytes: a sweep whose workspace does not hold it runs as one launch.
+struct SweepWs { float *part, *state; };
+static_assert(scn::SWEEP_PART_FLOATS % 32 == 0 && scn::sweep_state_floats(STRIVE_ZDIM) % 64 == 0 && scn::sweep_state_floats(scn::ZMAX) % 64 == 0,
+              "the stepwise sweep's arrays are whole 256-byte units: state follows part without a gap");
+
+SweepWs sweep_ws_layout(StriveArena& ar, int B, int K, int zw) {
+    SweepWs w;
+    ar.take<char>(256);
+    w.part = ar.take<float>(2 * (size_t)B * K * scn::SWEEP_PART_FLOATS);
+    w.state = ar.take<float>((size_t)B * K * scn::sweep_state_floats(zw));
+    ar.take<char>(256);
+    return w;
 }
 
 // What the training path wants on top of dL/dz (all device pointers; reference src/train_traffic.py:103-131 needs the
@@ -1107,6 +1126,18 @@ static size_t wjobs_tape_floats(const StriveGNN& g, size_t R, int max_n, int FT,
     return wjobs_plan(g, gr, gg, fake, R, max_n, FT, n_edges).tape_floats;
 }
 
+// the training sweep's workspace: the sweep's own workspace, then what TrainOut keeps beside it; the CNN backward gets the rest
+static void train_ws_layout(StriveArena& ar, const StriveDecoder* dec, const StriveScenes* sc, int FT, TrainOut& tr) {
+    const size_t R = (size_t)sc->NA * sc->NS, steps = FT > 1 ? (size_t)(FT - 1) : 1;
+    ar.take<char>(strive_rollout_workspace_bytes(dec, sc, FT));
+    tr.g_mf_all = ar.take<float>((size_t)FT * R * 64);
+    tr.mapix_all = ar.take<int32_t>(steps * R);
+    tr.jobs = ar.take<WJobTable>(1);
+    tr.wtape = ar.take<float>(wjobs_tape_floats(dec->gnn, R, sc->max_n, FT, sc->n_edges));
+    tr.cnn_ws_bytes = ar.ok() ? ar.cap - ar.off : 0;
+    tr.cnn_ws = ar.take<char>(strive_map_cnn_bwd_workspace_bytes((int32_t)(steps * R)));
+}
+
 
 // a library-owned stream per device for work that overlaps the caller's stream inside ONE call (forked and joined with events
 // before the call returns: the caller never sees it)
@@ -1148,24 +1179,15 @@ static SideStream* side_stream() {
 
 template <bool WG>
 int rollout_backward(const StriveDecoder* dec, const StriveScenes* sc, const float* lw, const float* sem, const float* z,
-                     const float* ext_future, int32_t FT, const float* d_traj, float* dz, const void* tape, size_t tape_bytes,
-                     void* ws, size_t ws_bytes, strive_stream_t stream_, const TrainOut* tr) {
+                     const float* ext_future, int32_t FT, const float* d_traj, float* dz, const Tape& tp, void* ws, size_t ws_bytes,
+                     strive_stream_t stream_, const TrainOut* tr) {
     const size_t R = (size_t)sc->NA * sc->NS;
     hipStream_t stream = (hipStream_t)stream_;
-    Tape tp = carve_tape(const_cast<void*>(tape), tape_bytes, R, FT, sc->max_n > 0 ? sc->max_n : 1);
     StriveArena ar(ws, ws_bytes);
-    float* g_state = ar.take<float>(R * 8);
-    float* g_pos = ar.take<float>(R * 4);
-    float* d_loc = ar.take<float>(R * 4);
-    float* g_pf = ar.take<float>(R * 64);
-    float* g_mf = ar.take<float>(R * 64);
-    (void)g_mf;             // (the training path keeps the map-feature adjoints of every step in TrainOut::g_mf_all)
-    float* g_mem = ar.take<float>(R * 192);
-    GnnBwdBuffers bw = gnn_bwd_buffers_take(ar, R, 64, sc->max_n);
+    const BwdWs w = bwd_ws_layout(ar, R, sc->max_n);
     if (!ar.ok()) { strive_set_error("rollout_bwd: workspace arena overflow"); return -1; }
 
-    const GNNDev gd = gnn_dev(dec->gnn);
-    const GRUDev gr = gru_dev(dec->gru);
+    const DecoderDev dd = decoder_dev(*dec);
     GNNGradDev ggn = gnn_grad_dev(dec->gnn, tr ? tr->d_gnn : nullptr);
     GRUGradDev ggr = gru_grad_dev(tr ? tr->d_gru : nullptr);
     WJobsPlan plan;
@@ -1181,7 +1203,6 @@ int rollout_backward(const StriveDecoder* dec, const StriveScenes* sc, const flo
         ggn.mlp_in.jobs = ggn.edge.jobs = ggn.update.jobs = ggn.mlp_out.jobs = tr->jobs;
         ggr.jobs = tr->jobs;
     }
-    const DynParams dp = dyn_params(*dec);
     const ScenesDev sd = scenes_dev(*sc);
     const int NC = dec->gnn.NC;
     const int in_ld1 = ld4(dec->gnn.mlp_in.dims[0]), xs_ld = ld4(64 + NC), in_ld2 = ld4(128 + NC);
@@ -1209,42 +1230,35 @@ int rollout_backward(const StriveDecoder* dec, const StriveScenes* sc, const flo
     if (tr && FT > 1)
         hipLaunchKernelGGL(tile_mapix_kernel, dim3((total_crops + 255) / 256), dim3(256), 0, stream, tr->mapix, tr->mapix_all, (int)R, total_crops);
 
-    hipMemsetAsync(g_state, 0, R * 8 * 4, stream);
-    hipMemsetAsync(g_pos, 0, R * 4 * 4, stream);
-    hipMemsetAsync(d_loc, 0, R * 4 * 4, stream);
-    hipMemsetAsync(g_pf, 0, R * 64 * 4, stream);
-    hipMemsetAsync(g_mem, 0, R * 192 * 4, stream);
+    hipMemsetAsync(w.g_state, 0, R * 8 * 4, stream);
+    hipMemsetAsync(w.g_pos, 0, R * 4 * 4, stream);
+    hipMemsetAsync(w.d_loc, 0, R * 4 * 4, stream);
+    hipMemsetAsync(w.g_pf, 0, R * 64 * 4, stream);
+    hipMemsetAsync(w.g_mem, 0, R * 192 * 4, stream);
     hipMemsetAsync(dz, 0, R * decoder_zdim(*dec) * 4, stream);
 
     for (int t = FT - 1; t >= 0; --t) {
-        GnnBuffers g2;
-        g2.A = tp.A_t(t);
-        g2.ARG = tp.ARG_t(t);
-        g2.X = tp.X_t(t);          // x, P, Q of step t as the forward sweep left them in the tape
-        g2.P = tp.P_t(t);
-        g2.Q = tp.Q_t(t);
-        g2.PRE_IN = tp.PRE_IN_t(t);
-        g2.PRE_E = tp.PRE_E_t(t);
+        const GnnBuffers g2 = tp.gnn_t(t);      // x, P, Q of step t as the forward sweep left them in the tape
         FeatSrc f = decoder_features(tp, t, sem, z, lw, NC, decoder_zdim(*dec));
         if (t < FT - 1)
-            hipLaunchKernelGGL(gru_bwd_kernel<WG>, dim3(nb), dim3(256), gru_bwd_lds_bytes(), stream, gr, ggr, tp, t, (int)R, g_pf,
-                               g_mem, d_loc);
+            hipLaunchKernelGGL(gru_bwd_kernel<WG>, dim3(nb), dim3(256), gru_bwd_lds_bytes(), stream, dd.gr, ggr, tp, t, (int)R, w.g_pf,
+                               w.g_mem, w.d_loc);
         Node2BwdArgs a2;
         a2.t = t; a2.FT = FT; a2.R = (int)R; a2.NS = sc->NS; a2.X = g2.X; a2.sem = sem; a2.lw = lw; a2.ext = ext_future;
-        a2.ptr = sc->ptr; a2.scene_of = sc->scene_of; a2.g_traj = d_traj; a2.g_pos = g_pos; a2.d_loc = d_loc;
-        a2.g_state = g_state; a2.dX = bw.dX; a2.dA = bw.dA;
+        a2.ptr = sc->ptr; a2.scene_of = sc->scene_of; a2.g_traj = d_traj; a2.g_pos = w.g_pos; a2.d_loc = w.d_loc;
+        a2.g_state = w.g_state; a2.dX = w.bw.dX; a2.dA = w.bw.dA;
         if (direct)
-            hipLaunchKernelGGL((node2_bwd_kernel<WG, true>), dim3(nb), dim3(256), node2_bwd_lds_bytes(in_ld2), stream, gd, ggn, dp, a2, tp);
+            hipLaunchKernelGGL((node2_bwd_kernel<WG, true>), dim3(nb), dim3(256), node2_bwd_lds_bytes(in_ld2), stream, dd.gd, ggn, dd.dp, a2, tp);
         else
-            hipLaunchKernelGGL((node2_bwd_kernel<WG, false>), dim3(nb), dim3(256), node2_bwd_lds_bytes(in_ld2), stream, gd, ggn, dp, a2, tp);
+            hipLaunchKernelGGL((node2_bwd_kernel<WG, false>), dim3(nb), dim3(256), node2_bwd_lds_bytes(in_ld2), stream, dd.gd, ggn, dd.dp, a2, tp);
         EdgeBwdArgs ae;
-        ae.dA = bw.dA; ae.ARG = tp.ARG_t(t); ae.dP = bw.dP; ae.DE1 = bw.DE1; ae.DPJ = bw.DPJ; ae.gpos_tgt = bw.gpos_tgt;
-        hipLaunchKernelGGL(edge_bwd_kernel<WG>, dim3((unsigned)R), dim3(256), edge_bwd_lds_bytes(), stream, gd, ggn, sd, tp.pos_t(t),
+        ae.dA = w.bw.dA; ae.ARG = tp.ARG_t(t); ae.dP = w.bw.dP; ae.DE1 = w.bw.DE1; ae.DPJ = w.bw.DPJ; ae.gpos_tgt = w.bw.gpos_tgt;
+        hipLaunchKernelGGL(edge_bwd_kernel<WG>, dim3((unsigned)R), dim3(256), edge_bwd_lds_bytes(), stream, dd.gd, ggn, sd, tp.pos_t(t),
                            g2, ae);
         Node1BwdArgs a1;
-        a1.t = t; a1.R = (int)R; a1.dX = bw.dX; a1.dP = bw.dP; a1.DE1 = bw.DE1; a1.DPJ = bw.DPJ; a1.gpos_tgt = bw.gpos_tgt;
-        a1.sem = sem; a1.PRE_IN = tp.PRE_IN_t(t); a1.X = g2.X; a1.g_pos = g_pos; a1.g_full = nullptr; a1.g_pf = g_pf; a1.g_mf = tr ? tr->g_mf_all + (size_t)t * R * 64 : nullptr; a1.dz = dz;
-        hipLaunchKernelGGL(node1_bwd_kernel<WG>, dim3(nb), dim3(256), node1_bwd_lds_bytes(in_ld1, xs_ld), stream, gd, ggn, sd, f, a1);
+        a1.t = t; a1.R = (int)R; a1.dX = w.bw.dX; a1.dP = w.bw.dP; a1.DE1 = w.bw.DE1; a1.DPJ = w.bw.DPJ; a1.gpos_tgt = w.bw.gpos_tgt;
+        a1.sem = sem; a1.PRE_IN = tp.PRE_IN_t(t); a1.X = g2.X; a1.g_pos = w.g_pos; a1.g_full = nullptr; a1.g_pf = w.g_pf; a1.g_mf = tr ? tr->g_mf_all + (size_t)t * R * 64 : nullptr; a1.dz = dz;
+        hipLaunchKernelGGL(node1_bwd_kernel<WG>, dim3(nb), dim3(256), node1_bwd_lds_bytes(in_ld1, xs_ld), stream, dd.gd, ggn, sd, f, a1);
         if (side && t >= 1 && ((t_hi - t + 1 >= grp && n_handed < SideStream::NEV - 1) || t == 1)) {
             // steps t .. t_hi are final: their crops are rows (t - 1) R .. t_hi R of the kept arrays (with more groups than events --
             // FT > 64 at one step per group -- the last group takes all remaining steps)
@@ -1283,7 +1297,7 @@ int rollout_backward(const StriveDecoder* dec, const StriveScenes* sc, const flo
         if (rc) return rc;
     }
     if (tr)
-        hipLaunchKernelGGL(rollout_init_bwd_kernel, dim3((unsigned)((R * 64 + 255) / 256)), dim3(256), 0, stream, g_pf, g_mem, tr->g_mf_all,
+        hipLaunchKernelGGL(rollout_init_bwd_kernel, dim3((unsigned)((R * 64 + 255) / 256)), dim3(256), 0, stream, w.g_pf, w.g_mem, tr->g_mf_all,
                            tr->d_past_feat, tr->d_map_feat, (int)R);
     return 0;
 }
@@ -1291,9 +1305,17 @@ int rollout_backward(const StriveDecoder* dec, const StriveScenes* sc, const flo
 
 extern "C" size_t strive_rollout_workspace_bytes(const StriveDecoder* dec, const StriveScenes* sc, int32_t FT) {
     if (!sc) return 0;
-    const size_t R = (size_t)sc->NA * sc->NS;
-    const size_t f = fwd_ws_bytes(R, fwd_part_elems(dec, sc)), b = bwd_ws_bytes(R, sc->max_n > 0 ? sc->max_n : 1);
+    const size_t f = strive_measure([&](StriveArena& ar) { fwd_ws_layout(ar, dec, *sc); });
+    const size_t b = strive_measure([&](StriveArena& ar) { bwd_ws_layout(ar, (size_t)sc->NA * sc->NS, clamped_max_n(*sc)); });
     return (f > b ? f : b) + 4096;
+}
+
+// one launch of scene_bwd_sweep_kernel (scene_rollout.h)
+template <bool PROF, bool STEP, int ZFIX>
+static void launch_scene_sweep(const DecoderDev& dd, const scn::SweepArgs& a, dim3 grid, const Tape& tp, unsigned long long* prof,
+                               hipStream_t stream) {
+    hipLaunchKernelGGL((scn::scene_bwd_sweep_kernel<PROF, STEP, ZFIX>), grid, dim3(scn::NTHR), scn::BwdLds<scn::sweep_zw(ZFIX)>::BYTES, stream,
+                       dd.gd, dd.gr, dd.gf, dd.dp, a, tp, prof);
 }
 
 extern "C" int strive_rollout_bwd(const StriveDecoder* dec, const StriveScenes* sc, const float* lw, const float* sem,
@@ -1301,20 +1323,23 @@ extern "C" int strive_rollout_bwd(const StriveDecoder* dec, const StriveScenes* 
                                   const void* tape, size_t tape_bytes, void* ws, size_t ws_bytes, strive_stream_t stream_) {
     STRIVE_CHECK_ARG(dec && sc && lw && sem && z && d_traj && dz && tape && ws, "null argument");
     if (check_decoder(dec, sc, FT)) return -1;
-    const size_t R = (size_t)sc->NA * sc->NS;
-    if (R == 0) return 0;
-    STRIVE_CHECK_ARG(tape_bytes >= tape_bytes_for(R, FT, sc->max_n > 0 ? sc->max_n : 1), "tape too small");
+    if ((size_t)sc->NA * sc->NS == 0) return 0;
+    Tape tp;
+    STRIVE_CHECK_ARG(carve_tape(*sc, FT, tape, tape_bytes, tp), "tape too small");
     STRIVE_CHECK_ARG(ws_bytes >= strive_rollout_workspace_bytes(dec, sc, FT), "workspace too small");
     STRIVE_CHECK_ARG(sc->max_n >= 1, "max_n not set");
     if (scene_kernels_on(dec, sc)) {
         // the whole reverse sweep of a scene in one launch (scene_rollout.h)
         if (scene_kernels_prepare()) return -1;
-        Tape tp = carve_tape(const_cast<void*>(tape), tape_bytes, R, FT, sc->max_n);
+        hipStream_t stream = (hipStream_t)stream_;
+        const DecoderDev dd = decoder_dev(*dec);
+        const dim3 grid((unsigned)sc->B);
         scn::SweepArgs a;
         a.FT = FT; a.NC = dec->gnn.NC; a.max_n = sc->max_n; a.sem = sem; a.lw = lw; a.ext = ext_future; a.ptr = sc->ptr;
         a.par = dec->scene_par; a.g_traj = d_traj; a.dz = dz;
-        // option scene_prof = 1 (tools/scene_phase_probe.py): workgroup 0 adds the core-clock ticks of every phase to 16 counters at the
-        // start of the workspace, which this path does not use otherwise
+        a.t = 0; a.K = 1; a.part = nullptr; a.state = nullptr;
+        // option scene_prof = 1 (tools/scene_phase_probe.py): workgroup 0 adds the core-clock ticks of every phase to 16 counters 256
+        // bytes into the workspace, which this path does not use otherwise
         const bool prof = strive_tuning().scene_prof != 0;
         // Stepwise form: one launch per reverse step, K workgroups per scene sharing the scene's edge chunks (scene_rollout.h).
         // Default from 3 chunks per scene on (>= 12 agents: 132 edge rows); option sweep_step = 0 (never) | K (1..4, forced).
@@ -1324,36 +1349,21 @@ extern "C" int strive_rollout_bwd(const StriveDecoder* dec, const StriveScenes* 
         if (K > 4) K = 4;
         scene_form(*dec, [&](auto, auto zfix) {
             constexpr int ZFIX = decltype(zfix)::value;
-            constexpr size_t LDS = scn::BwdLds<scn::sweep_zw(ZFIX)>::BYTES;
-            const size_t need =
-                (size_t)sc->B * (K > 0 ? K : 1) * (2 * scn::SWEEP_PART_FLOATS + scn::sweep_state_floats(scn::sweep_zw(ZFIX))) * 4 + 512;
-            if (K >= 1 && !prof && ws_bytes >= need) {
-                a.K = K;
-                a.part = reinterpret_cast<float*>((char*)ws + 256);
-                a.state = a.part + 2 * (size_t)sc->B * K * scn::SWEEP_PART_FLOATS;
-                const GNNDev gd = gnn_dev(dec->gnn);
-                const GRUDev gr = gru_dev(dec->gru);
-                const scn::GRUFrag gf = scn::gru_frag(dec->gru);
-                const DynParams dp = dyn_params(*dec);
-                for (int t = FT - 1; t >= -1; --t) {
-                    a.t = t;
-                    hipLaunchKernelGGL((scn::scene_bwd_sweep_kernel<false, true, ZFIX>), dim3((unsigned)sc->B, (unsigned)K), dim3(scn::NTHR), LDS,
-                                       (hipStream_t)stream_, gd, gr, gf, dp, a, tp, (unsigned long long*)nullptr);
-                }
-                return;
+            StriveArena ar(ws, ws_bytes);
+            const SweepWs sw = sweep_ws_layout(ar, sc->B, K > 0 ? K : 1, scn::sweep_zw(ZFIX));
+            if (K >= 1 && !prof && ar.ok()) {
+                a.K = K; a.part = sw.part; a.state = sw.state;
+                for (a.t = FT - 1; a.t >= -1; --a.t) launch_scene_sweep<false, true, ZFIX>(dd, a, dim3((unsigned)sc->B, (unsigned)K), tp, nullptr, stream);
+            } else if (prof) {
+                launch_scene_sweep<true, false, ZFIX>(dd, a, grid, tp, (unsigned long long*)ws + 32, stream);
+            } else {
+                launch_scene_sweep<false, false, ZFIX>(dd, a, grid, tp, nullptr, stream);
             }
-            a.t = 0; a.K = 1; a.part = nullptr; a.state = nullptr;
-            if (prof)
-                hipLaunchKernelGGL((scn::scene_bwd_sweep_kernel<true, false, ZFIX>), dim3((unsigned)sc->B), dim3(scn::NTHR), LDS, (hipStream_t)stream_,
-                                   gnn_dev(dec->gnn), gru_dev(dec->gru), scn::gru_frag(dec->gru), dyn_params(*dec), a, tp, (unsigned long long*)ws + 32);
-            else
-                hipLaunchKernelGGL((scn::scene_bwd_sweep_kernel<false, false, ZFIX>), dim3((unsigned)sc->B), dim3(scn::NTHR), LDS, (hipStream_t)stream_,
-                                   gnn_dev(dec->gnn), gru_dev(dec->gru), scn::gru_frag(dec->gru), dyn_params(*dec), a, tp, (unsigned long long*)nullptr);
         });
         STRIVE_CHECK_LAUNCH();
         return 0;
     }
-    int rc = rollout_backward<false>(dec, sc, lw, sem, z, ext_future, FT, d_traj, dz, tape, tape_bytes, ws, ws_bytes, stream_, nullptr);
+    int rc = rollout_backward<false>(dec, sc, lw, sem, z, ext_future, FT, d_traj, dz, tp, ws, ws_bytes, stream_, nullptr);
     if (rc) return rc;
     STRIVE_CHECK_LAUNCH();
     return 0;
@@ -1361,10 +1371,8 @@ extern "C" int strive_rollout_bwd(const StriveDecoder* dec, const StriveScenes* 
 
 extern "C" size_t strive_rollout_train_workspace_bytes(const StriveDecoder* dec, const StriveScenes* sc, int32_t FT) {
     if (!sc) return 0;
-    const size_t R = (size_t)sc->NA * sc->NS, steps = FT > 1 ? (size_t)(FT - 1) : 1;
-    return strive_rollout_workspace_bytes(dec, sc, FT) + strive_align_up(strive_map_cnn_bwd_workspace_bytes((int32_t)(steps * R)), 256) +
-           strive_align_up((size_t)FT * R * 64 * 4, 256) + strive_align_up(steps * R * 4, 256) +
-           strive_align_up(sizeof(WJobTable), 256) + strive_align_up(wjobs_tape_floats(dec->gnn, R, sc->max_n, FT, sc->n_edges) * 4, 256);
+    TrainOut tr;
+    return strive_measure([&](StriveArena& ar) { train_ws_layout(ar, dec, sc, FT, tr); });
 }
 
 extern "C" size_t strive_gnn_param_count(const StriveGNN* gnn) { return gnn ? gnn_param_count(*gnn) : 0; }
@@ -1379,33 +1387,21 @@ static int rollout_backward_train(const StriveDecoder* dec, const StriveScenes* 
                      tape && ws, "null argument");
     if (check_decoder(dec, sc, FT)) return -1;
     STRIVE_CHECK_ARG(sc->NS == 1, "the training backward takes 2-D latents (one sample per agent)");
-    const size_t R = (size_t)sc->NA;
-    if (R == 0) return 0;
-    STRIVE_CHECK_ARG(tape_bytes >= tape_bytes_for(R, FT, sc->max_n > 0 ? sc->max_n : 1), "tape too small");
+    if (sc->NA == 0) return 0;
+    Tape tp;
+    STRIVE_CHECK_ARG(carve_tape(*sc, FT, tape, tape_bytes, tp), "tape too small");
     STRIVE_CHECK_ARG(ws_bytes >= strive_rollout_train_workspace_bytes(dec, sc, FT), "workspace too small");
     STRIVE_CHECK_ARG(sc->max_n >= 1, "max_n not set");
-    const size_t base = strive_rollout_workspace_bytes(dec, sc, FT);
     STRIVE_CHECK_ARG(!kept || kept_bytes >= strive_rollout_keep_bytes(dec, sc, FT), "kept-activation buffer too small");
     TrainOut tr;
     tr.d_past_feat = d_past_feat; tr.d_map_feat = d_map_feat; tr.d_gnn = d_gnn; tr.d_gru = d_gru; tr.d_cnn = d_cnn;
     tr.mapix = mapix;
     tr.kept = kept; tr.kept_bytes = kept_bytes;
-    {
-        const size_t steps = FT > 1 ? (size_t)(FT - 1) : 1;
-        char* p = (char*)ws + base;
-        tr.g_mf_all = (float*)p;
-        p += strive_align_up((size_t)FT * R * 64 * 4, 256);
-        tr.mapix_all = (int32_t*)p;
-        p += strive_align_up(steps * R * 4, 256);
-        const bool atomics_only = strive_tuning().wgrad_atomics != 0;      // A/B switch: no deferred weight gradients
-        tr.jobs = atomics_only ? nullptr : (WJobTable*)p;
-        p += strive_align_up(sizeof(WJobTable), 256);
-        tr.wtape = (float*)p;
-        p += strive_align_up(wjobs_tape_floats(dec->gnn, R, sc->max_n, FT, sc->n_edges) * 4, 256);
-        tr.cnn_ws = p;
-        tr.cnn_ws_bytes = ws_bytes - (size_t)(p - (char*)ws);
-    }
-    int rc = rollout_backward<true>(dec, sc, lw, sem, z, ext_future, FT, d_traj, dz, tape, tape_bytes, ws, base, stream_, &tr);
+    StriveArena ar(ws, ws_bytes);
+    train_ws_layout(ar, dec, sc, FT, tr);
+    if (strive_tuning().wgrad_atomics != 0) tr.jobs = nullptr;      // A/B switch: no deferred weight gradients
+    int rc = rollout_backward<true>(dec, sc, lw, sem, z, ext_future, FT, d_traj, dz, tp, ws, strive_rollout_workspace_bytes(dec, sc, FT),
+                                    stream_, &tr);
     if (rc) return rc;
     STRIVE_CHECK_LAUNCH();
     return 0;

@@ -102,21 +102,8 @@ static inline bool supported(const StriveDecoder& d, const StriveScenes& sc, boo
 
 // ---------------------------------------------------------------------------------------------------------------------
 // 16-lane row groups: lane = 16 * sub + q; a wave instruction works on 4 rows, lane q of a group on 8 consecutive channels
+// (reductions inside a group: common.h row16_sum / row16_max)
 // ---------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float grp_sum(float v) {
-    v += dpp_move<STRIVE_DPP_QUAD_XOR1>(v);
-    v += dpp_move<STRIVE_DPP_QUAD_XOR2>(v);
-    v += dpp_move<STRIVE_DPP_ROW_HALF_MIRROR>(v);
-    v += dpp_move<STRIVE_DPP_ROW_MIRROR>(v);
-    return v;
-}
-__device__ __forceinline__ float grp_max(float v) {
-    v = fmaxf(v, dpp_move<STRIVE_DPP_QUAD_XOR1>(v));
-    v = fmaxf(v, dpp_move<STRIVE_DPP_QUAD_XOR2>(v));
-    v = fmaxf(v, dpp_move<STRIVE_DPP_ROW_HALF_MIRROR>(v));
-    v = fmaxf(v, dpp_move<STRIVE_DPP_ROW_MIRROR>(v));
-    return v;
-}
 
 // power of two that brings mx into [2^14, 2^15) (mlp_dev.h dense_mfma)
 __device__ __forceinline__ float pow2_scale(float mx) {
@@ -173,7 +160,7 @@ __device__ __forceinline__ void split16(Src src, int IN, int KP, int nrows, int 
                 mx = fmaxf(mx, fabsf(x));
             }
         }
-        mx = grp_max(mx);
+        mx = row16_max(mx);
         const float sc = pow2_scale(mx);
         if (r < rows_pad) {
 #pragma unroll
@@ -215,18 +202,18 @@ __device__ __forceinline__ void ln_relu_split16(RowPtr xrow, int nrows, int rows
         float s = 0.f;
 #pragma unroll
         for (int i = 0; i < 8; ++i) s += x[i];
-        const float mean = grp_sum(s) / 128.0f;
+        const float mean = row16_sum(s) / 128.0f;
         float v = 0.f;
 #pragma unroll
         for (int i = 0; i < 8; ++i) { const float d = x[i] - mean; v = fmaf(d, d, v); }
-        const float rstd = 1.0f / sqrtf(grp_sum(v) / 128.0f + LN_EPS);
+        const float rstd = 1.0f / sqrtf(row16_sum(v) / 128.0f + LN_EPS);
         float y[8], mx = 0.f;
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
             y[i] = live ? fmaxf((x[i] - mean) * rstd * g8[i] + b8[i], 0.f) : 0.f;
             mx = fmaxf(mx, y[i]);
         }
-        mx = grp_max(mx);
+        mx = row16_max(mx);
         const float sc = pow2_scale(mx);
         if (r < rows_pad) {
             if (f32 && live) {
@@ -292,11 +279,11 @@ __device__ __forceinline__ void ln_relu_bwd16(const XR<MAXIT>& xr, DyFn dy, int 
         float s = 0.f;
 #pragma unroll
         for (int i = 0; i < 8; ++i) s += x[i];
-        const float mean = grp_sum(s) / 128.0f;
+        const float mean = row16_sum(s) / 128.0f;
         float v = 0.f;
 #pragma unroll
         for (int i = 0; i < 8; ++i) { const float dd = x[i] - mean; v = fmaf(dd, dd, v); }
-        const float rstd = 1.0f / sqrtf(grp_sum(v) / 128.0f + LN_EPS);
+        const float rstd = 1.0f / sqrtf(row16_sum(v) / 128.0f + LN_EPS);
         float xh[8], gg[8], m1 = 0.f, m2 = 0.f;
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
@@ -307,15 +294,15 @@ __device__ __forceinline__ void ln_relu_bwd16(const XR<MAXIT>& xr, DyFn dy, int 
             m1 += gg[i];
             m2 = fmaf(gg[i], xh[i], m2);
         }
-        m1 = grp_sum(m1) / 128.0f;
-        m2 = grp_sum(m2) / 128.0f;
+        m1 = row16_sum(m1) / 128.0f;
+        m2 = row16_sum(m2) / 128.0f;
         float dx[8], mx = 0.f;
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
             dx[i] = live ? rstd * (gg[i] - m1 - xh[i] * m2) : 0.f;
             mx = fmaxf(mx, fabsf(dx[i]));
         }
-        mx = grp_max(mx);
+        mx = row16_max(mx);
         if (out && live) {
             float4* o = reinterpret_cast<float4*>(out + (size_t)r * out_ld + 8 * q);
             o[0] = make_float4(dx[0], dx[1], dx[2], dx[3]);
@@ -875,11 +862,11 @@ static __global__ __launch_bounds__(NTHR) void scene_fwd_step_kernel(GNNDev g, G
             float s = 0.f;
 #pragma unroll
             for (int i = 0; i < 8; ++i) s += x[i];
-            const float mean = grp_sum(s) / 128.0f;
+            const float mean = row16_sum(s) / 128.0f;
             float v = 0.f;
 #pragma unroll
             for (int i = 0; i < 8; ++i) { const float d = x[i] - mean; v = fmaf(d, d, v); }
-            const float rstd = 1.0f / sqrtf(grp_sum(v) / 128.0f + LN_EPS);
+            const float rstd = 1.0f / sqrtf(row16_sum(v) / 128.0f + LN_EPS);
             float d0 = 0.f, d1 = 0.f;
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
@@ -888,8 +875,8 @@ static __global__ __launch_bounds__(NTHR) void scene_fwd_step_kernel(GNNDev g, G
                 d0 = fmaf(y, W2[c], d0);
                 d1 = fmaf(y, W2[H + c], d1);
             }
-            d0 = grp_sum(d0);
-            d1 = grp_sum(d1);
+            d0 = row16_sum(d0);
+            d1 = row16_sum(d1);
             if (live && q == 0) {
                 s_dec[r * 4 + 0] = d0 + (L.par + Par::O_B2)[0];
                 s_dec[r * 4 + 1] = d1 + (L.par + Par::O_B2)[1];
@@ -1227,7 +1214,7 @@ static __global__ __launch_bounds__(NTHR) void scene_bwd_sweep_kernel(GNNDev g, 
                             }
                         }
 #pragma unroll
-                        for (int k = 0; k < 4; ++k) v[k] = grp_sum(v[k]);
+                        for (int k = 0; k < 4; ++k) v[k] = row16_sum(v[k]);
                         if (rr < n && q == 0)
                             for (int k = 0; k < 4; ++k) L.d_loc[rr * 4 + k] = v[k];
                     }
@@ -1471,7 +1458,7 @@ static __global__ __launch_bounds__(NTHR) void scene_bwd_sweep_kernel(GNNDev g, 
                             }
                         }
 #pragma unroll
-                        for (int d = 0; d < 4; ++d) v[d] = grp_sum(v[d]);
+                        for (int d = 0; d < 4; ++d) v[d] = row16_sum(v[d]);
                         if (r < ne && q == 0)
                             for (int d = 0; d < 4; ++d) s_grel[r * 4 + d] = v[d];
                     }

@@ -726,34 +726,58 @@ class _RolloutCtx(object):
     pass
 
 
+def _rollout_fwd(h, zz, past_feat, map_feat, kept=None):
+    """strive_rollout_fwd over the latent rows ``zz`` (R, Z) -> (traj (R, FT, 4), tape); with ``kept`` strive_rollout_fwd_keep, which
+    also leaves the map CNN's activations of the re-encoded steps there (for strive_rollout_bwd_train_kept)"""
+    dev = zz.device
+    traj = torch.empty((h.R, h.FT, 4), dtype=torch.float32, device=dev)
+    tape = torch.empty(h.tape_bytes, dtype=torch.uint8, device=dev)
+    ws = _workspace(dev, h.ws_bytes, 'rollout')
+    keep = () if kept is None else (L.ptr(kept), kept.numel())
+    h.lib.call('strive_rollout_fwd' if kept is None else 'strive_rollout_fwd_keep', h.dec.ref(), h.sc.ref(), L.ptr(h.past_last), L.ptr(h.lw),
+               L.ptr(h.sem), L.ptr(past_feat), L.ptr(map_feat), L.ptr(zz), L.ptr(h.mapix), L.ptr(h.ext), h.FT, L.ptr(traj), L.ptr(tape),
+               tape.numel(), L.ptr(ws), ws.numel(), *keep, _stream(zz))
+    return traj, tape
+
+
+def _rollout_sweep(h, zz, tape, d_traj, ws=None):
+    """strive_rollout_bwd: dL/dz (R, Z) of the trajectory adjoint ``d_traj`` (R, FT, 4, fp32) over the forward's tape; ``ws``: the
+    scratch of the stream the sweep runs on when the caller has fetched it already"""
+    dev = d_traj.device
+    dz = torch.empty((h.R, h.Z), dtype=torch.float32, device=dev)
+    ws = _workspace(dev, h.ws_bytes, 'rollout') if ws is None else ws
+    h.lib.call('strive_rollout_bwd', h.dec.ref(), h.sc.ref(), L.ptr(h.lw), L.ptr(h.sem), L.ptr(zz), L.ptr(h.ext), h.FT, L.ptr(d_traj),
+               L.ptr(dz), L.ptr(tape), tape.numel(), L.ptr(ws), ws.numel(), _stream(d_traj))
+    return dz
+
+
+def _rollout_train_sweep(h, zz, tape, d_traj, flat_grads, kept=None):
+    """strive_rollout_bwd_train (``kept``: strive_rollout_bwd_train_kept on the forward's map-CNN activations): the weight gradients
+    are added to the three flat blocks ``flat_grads`` (decoder_net | decoder_memory | map_conv + map_feature) -> dz, d past_feat,
+    d map_feat"""
+    lib, dev = h.lib, d_traj.device
+    dz = torch.empty((h.R, h.Z), dtype=torch.float32, device=dev)
+    dpf = torch.empty((h.R, 64), dtype=torch.float32, device=dev)
+    dmf = torch.empty((h.R, 64), dtype=torch.float32, device=dev)
+    ws = _workspace(dev, lib.query('strive_rollout_train_workspace_bytes', h.dec.ref(), h.sc.ref(), h.FT), 'rollout_train')
+    keep = () if kept is None else (L.ptr(kept), kept.numel())
+    lib.call('strive_rollout_bwd_train' if kept is None else 'strive_rollout_bwd_train_kept', h.dec.ref(), h.sc.ref(), L.ptr(h.lw),
+             L.ptr(h.sem), L.ptr(zz), L.ptr(h.ext), L.ptr(h.mapix), h.FT, L.ptr(d_traj), L.ptr(dz), L.ptr(dpf), L.ptr(dmf),
+             *[L.ptr(g) for g in flat_grads], L.ptr(tape), tape.numel(), *keep, L.ptr(ws), ws.numel(), _stream(d_traj))
+    return dz, dpf, dmf
+
+
 class _RolloutFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, z, h):
-        lib = h.lib
-        dev = z.device
         zz = _f32c(z).reshape(h.R, h.Z)
-        traj = torch.empty((h.R, h.FT, 4), dtype=torch.float32, device=dev)
-        tape = torch.empty(h.tape_bytes, dtype=torch.uint8, device=dev)
-        ws = _workspace(dev, h.ws_bytes, 'rollout')
-        lib.call('strive_rollout_fwd', h.dec.ref(), h.sc.ref(), L.ptr(h.past_last), L.ptr(h.lw), L.ptr(h.sem),
-                 L.ptr(h.past_feat), L.ptr(h.map_feat), L.ptr(zz), L.ptr(h.mapix), L.ptr(h.ext), h.FT, L.ptr(traj),
-                 L.ptr(tape), tape.numel(), L.ptr(ws), ws.numel(), _stream(z))
-        ctx.h = h
-        ctx.tape = tape
-        ctx.zz = zz
-        ctx.zshape = z.shape
+        traj, tape = _rollout_fwd(h, zz, h.past_feat, h.map_feat)
+        ctx.h, ctx.tape, ctx.zz, ctx.zshape = h, tape, zz, z.shape
         return traj
 
     @staticmethod
     def backward(ctx, d_traj):
-        h = ctx.h
-        dev = d_traj.device
-        dz = torch.empty((h.R, h.Z), dtype=torch.float32, device=dev)
-        ws = _workspace(dev, h.ws_bytes, 'rollout')
-        h.lib.call('strive_rollout_bwd', h.dec.ref(), h.sc.ref(), L.ptr(h.lw), L.ptr(h.sem), L.ptr(ctx.zz), L.ptr(h.ext),
-                   h.FT, L.ptr(_f32c(d_traj)), L.ptr(dz), L.ptr(ctx.tape), ctx.tape.numel(), L.ptr(ws), ws.numel(),
-                   _stream(d_traj))
-        return dz.reshape(ctx.zshape), None
+        return _rollout_sweep(ctx.h, ctx.zz, ctx.tape, _f32c(d_traj)).reshape(ctx.zshape), None
 
 
 _pair_streams = {}
@@ -770,7 +794,6 @@ class _RolloutPairFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, z_a, z_b, h):
-        lib = h.lib
         dev = z_a.device
         if os.environ.get('STRIVE_CHECK_PAIR') == '1' and not (dev.type == 'cuda' and torch.cuda.is_current_stream_capturing()):
             # debug aid (one host synchronisation per call; the GPU tests set it): only z_a is rolled out, so a caller whose two
@@ -779,12 +802,7 @@ class _RolloutPairFn(torch.autograd.Function):
                 raise ValueError('decode_embedding_pair: the two latents must hold the same values (complementary detach of the '
                                  'same leaves); use two decode_embedding calls for different latents')
         zz = _f32c(z_a).reshape(h.R, h.Z)
-        traj = torch.empty((h.R, h.FT, 4), dtype=torch.float32, device=dev)
-        tape = torch.empty(h.tape_bytes, dtype=torch.uint8, device=dev)
-        ws = _workspace(dev, h.ws_bytes, 'rollout')
-        lib.call('strive_rollout_fwd', h.dec.ref(), h.sc.ref(), L.ptr(h.past_last), L.ptr(h.lw), L.ptr(h.sem),
-                 L.ptr(h.past_feat), L.ptr(h.map_feat), L.ptr(zz), L.ptr(h.mapix), L.ptr(h.ext), h.FT, L.ptr(traj),
-                 L.ptr(tape), tape.numel(), L.ptr(ws), ws.numel(), _stream(z_a))
+        traj, tape = _rollout_fwd(h, zz, h.past_feat, h.map_feat)
         ctx.h, ctx.tape, ctx.zz = h, tape, zz
         ctx.shape_a, ctx.shape_b = z_a.shape, z_b.shape
         # a port without an incoming adjoint gets None, not zeros: the closed loop differentiates port B's loss while the planner
@@ -797,12 +815,6 @@ class _RolloutPairFn(torch.autograd.Function):
         h = ctx.h
         dev = (d_a if d_a is not None else d_b).device
         ws = _workspace(dev, h.ws_bytes, 'rollout')
-
-        def sweep(d_traj):
-            dz = torch.empty((h.R, h.Z), dtype=torch.float32, device=dev)
-            h.lib.call('strive_rollout_bwd', h.dec.ref(), h.sc.ref(), L.ptr(h.lw), L.ptr(h.sem), L.ptr(ctx.zz), L.ptr(h.ext),
-                       h.FT, L.ptr(d_traj), L.ptr(dz), L.ptr(ctx.tape), ctx.tape.numel(), L.ptr(ws), ws.numel(), _stream(d_traj))
-            return dz
         ga = gb = None
         want_a = ctx.needs_input_grad[0] and d_a is not None
         want_b = ctx.needs_input_grad[1] and d_b is not None
@@ -821,16 +833,13 @@ class _RolloutPairFn(torch.autograd.Function):
                     _pair_streams[str(dev)] = side
                 side.wait_stream(cur)
                 with torch.cuda.stream(side):
-                    ws_b = _workspace(dev, h.ws_bytes, 'rollout')          # (scratch is per stream)
-                    dzb = torch.empty((h.R, h.Z), dtype=torch.float32, device=dev)
-                    h.lib.call('strive_rollout_bwd', h.dec.ref(), h.sc.ref(), L.ptr(h.lw), L.ptr(h.sem), L.ptr(ctx.zz), L.ptr(h.ext),
-                               h.FT, L.ptr(db), L.ptr(dzb), L.ptr(ctx.tape), ctx.tape.numel(), L.ptr(ws_b), ws_b.numel(), _stream(db))
+                    gb = _rollout_sweep(h, ctx.zz, ctx.tape, db, _workspace(dev, h.ws_bytes, 'rollout'))      # (scratch is per stream)
                 db.record_stream(side)
-                gb = dzb.reshape(ctx.shape_b)
+                gb = gb.reshape(ctx.shape_b)
             else:
-                gb = sweep(db).reshape(ctx.shape_b)
+                gb = _rollout_sweep(h, ctx.zz, ctx.tape, db, ws).reshape(ctx.shape_b)
         if want_a:
-            ga = sweep(_f32c(d_a)).reshape(ctx.shape_a)
+            ga = _rollout_sweep(h, ctx.zz, ctx.tape, _f32c(d_a), ws).reshape(ctx.shape_a)
         if side is not None:
             torch.cuda.current_stream(dev).wait_stream(side)
             gb.record_stream(torch.cuda.current_stream(dev))
@@ -843,25 +852,11 @@ class _RolloutTrainFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, z, past_feat, map_feat, h, *ps):
-        lib = h.lib
-        dev = z.device
-        zz = z.to(torch.float32).contiguous().reshape(h.R, h.Z)
-        pf = past_feat.to(torch.float32).contiguous()
-        mf = map_feat.to(torch.float32).contiguous()
-        traj = torch.empty((h.R, h.FT, 4), dtype=torch.float32, device=dev)
-        tape = torch.empty(h.tape_bytes, dtype=torch.uint8, device=dev)
-        ws = _workspace(dev, h.ws_bytes, 'rollout')
+        zz = _f32c(z).reshape(h.R, h.Z)
         ctx.kept = None
         if keep_cnn_activations() and h.FT > 1:
-            ctx.kept = _alloc_kept(lib.query('strive_rollout_keep_bytes', h.dec.ref(), h.sc.ref(), h.FT), dev)
-        if ctx.kept is not None:
-            lib.call('strive_rollout_fwd_keep', h.dec.ref(), h.sc.ref(), L.ptr(h.past_last), L.ptr(h.lw), L.ptr(h.sem), L.ptr(pf),
-                     L.ptr(mf), L.ptr(zz), L.ptr(h.mapix), L.ptr(h.ext), h.FT, L.ptr(traj), L.ptr(tape), tape.numel(), L.ptr(ws),
-                     ws.numel(), L.ptr(ctx.kept), ctx.kept.numel(), _stream(z))
-        else:
-            lib.call('strive_rollout_fwd', h.dec.ref(), h.sc.ref(), L.ptr(h.past_last), L.ptr(h.lw), L.ptr(h.sem), L.ptr(pf), L.ptr(mf),
-                     L.ptr(zz), L.ptr(h.mapix), L.ptr(h.ext), h.FT, L.ptr(traj), L.ptr(tape), tape.numel(), L.ptr(ws), ws.numel(),
-                     _stream(z))
+            ctx.kept = _alloc_kept(h.lib.query('strive_rollout_keep_bytes', h.dec.ref(), h.sc.ref(), h.FT), z.device)
+        traj, tape = _rollout_fwd(h, zz, _f32c(past_feat), _f32c(map_feat), ctx.kept)
         ctx.h, ctx.tape, ctx.zz, ctx.zshape, ctx.ps = h, tape, zz, z.shape, ps
         return traj
 
@@ -869,10 +864,6 @@ class _RolloutTrainFn(torch.autograd.Function):
     def backward(ctx, d_traj):
         h = ctx.h
         lib = h.lib
-        dev = d_traj.device
-        dz = torch.empty((h.R, h.Z), dtype=torch.float32, device=dev)
-        dpf = torch.empty((h.R, 64), dtype=torch.float32, device=dev)
-        dmf = torch.empty((h.R, 64), dtype=torch.float32, device=dev)
         ng = lib.query('strive_gnn_param_count', C.byref(h.dec.struct.gnn))
         nr = lib.query('strive_gru_param_count')
         nc = lib.query('strive_map_cnn_param_count')
@@ -885,19 +876,9 @@ class _RolloutTrainFn(torch.autograd.Function):
                 sub.append(ps[k]); tot += ps[k].numel(); k += 1
             assert tot == c, 'parameter list does not match the flat gradient layout'
             blocks.append(sub)
-        targets = [_grad_target(sub, c, dev) for sub, c in zip(blocks, counts)]
-        wsb = lib.query('strive_rollout_train_workspace_bytes', h.dec.ref(), h.sc.ref(), h.FT)
-        ws = _workspace(dev, wsb, 'rollout_train')
-        if ctx.kept is not None:
-            lib.call('strive_rollout_bwd_train_kept', h.dec.ref(), h.sc.ref(), L.ptr(h.lw), L.ptr(h.sem), L.ptr(ctx.zz), L.ptr(h.ext),
-                     L.ptr(h.mapix), h.FT, L.ptr(_f32c(d_traj)), L.ptr(dz), L.ptr(dpf), L.ptr(dmf), L.ptr(targets[0][0]),
-                     L.ptr(targets[1][0]), L.ptr(targets[2][0]), L.ptr(ctx.tape), ctx.tape.numel(), L.ptr(ctx.kept), ctx.kept.numel(),
-                     L.ptr(ws), ws.numel(), _stream(d_traj))
-            ctx.kept = None
-        else:
-            lib.call('strive_rollout_bwd_train', h.dec.ref(), h.sc.ref(), L.ptr(h.lw), L.ptr(h.sem), L.ptr(ctx.zz), L.ptr(h.ext),
-                     L.ptr(h.mapix), h.FT, L.ptr(_f32c(d_traj)), L.ptr(dz), L.ptr(dpf), L.ptr(dmf), L.ptr(targets[0][0]),
-                     L.ptr(targets[1][0]), L.ptr(targets[2][0]), L.ptr(ctx.tape), ctx.tape.numel(), L.ptr(ws), ws.numel(), _stream(d_traj))
+        targets = [_grad_target(sub, c, d_traj.device) for sub, c in zip(blocks, counts)]
+        dz, dpf, dmf = _rollout_train_sweep(h, ctx.zz, ctx.tape, _f32c(d_traj), [flat for flat, _ in targets], ctx.kept)
+        ctx.kept = None
         grads = ()
         for (flat, give_back), sub in zip(targets, blocks):
             grads += _grad_return(flat, sub, give_back)
@@ -973,13 +954,17 @@ def decoder_rollout_pair(model, g, map_feat, past_feat, z_a, z_b, map_idx, map_e
     return ta.reshape(info.NA, h.FT, 4), tb.reshape(info.NA, h.FT_b, 4)
 
 
+def _rollout_train_params(model):
+    """the parameters the training rollout differentiates, in the order of its three flat gradient blocks"""
+    return list(model.decoder_net.parameters()) + list(model.decoder_memory.parameters()) + _cnn_params(model)
+
+
 def decoder_rollout(model, g, map_feat, past_feat, z, map_idx, map_env, ext_future, FT):
     """autoregressive_decoder as one fused call; differentiable w.r.t. ``z`` only."""
     train = _wgrad()
     h, info, multi, NS = _rollout_context(model, g, map_feat, past_feat, z, map_idx, map_env, ext_future, FT, train)
     if train:
-        ps = list(model.decoder_net.parameters()) + list(model.decoder_memory.parameters()) + _cnn_params(model)
-        traj = _RolloutTrainFn.apply(z, past_feat, map_feat, h, *ps)
+        traj = _RolloutTrainFn.apply(z, past_feat, map_feat, h, *_rollout_train_params(model))
         return traj.reshape(info.NA, h.FT, 4)
     traj = _RolloutFn.apply(z, h)
     return traj.reshape(info.NA, NS, h.FT, 4) if multi else traj.reshape(info.NA, h.FT, 4)
@@ -1000,8 +985,7 @@ def decoder_rollout_stacked(model, g, map_feat, past_feat, zs, map_idx, map_env,
     h, info, _, _ = _rollout_context(model, g, map_feat, past_feat, zs[0], map_idx, map_env, None, FT, train, copies=k)
     z = torch.cat(list(zs), 0)
     if train:
-        ps = list(model.decoder_net.parameters()) + list(model.decoder_memory.parameters()) + _cnn_params(model)
-        traj = _RolloutTrainFn.apply(z, torch.cat([past_feat] * k, 0), torch.cat([map_feat] * k, 0), h, *ps)
+        traj = _RolloutTrainFn.apply(z, torch.cat([past_feat] * k, 0), torch.cat([map_feat] * k, 0), h, *_rollout_train_params(model))
     else:
         traj = _RolloutFn.apply(z, h)
     return list(traj.reshape(k, info.NA, h.FT, 4).unbind(0))

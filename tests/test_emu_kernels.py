@@ -782,6 +782,101 @@ def test_fused_loss_workspace_sizes_are_pinned(emu, case, monkeypatch):
     assert bool((ws[nbytes:] == 0xFF).all()), 'AdvGenLoss wrote behind its workspace'
 
 
+# (strive_rollout_tape_bytes, strive_rollout_workspace_bytes, strive_rollout_train_workspace_bytes, strive_rollout_keep_bytes) per
+# shape.  `was`: from the library as it was BEFORE every rollout buffer's layout became one function that both measures and carves
+# (upper bounds: no size may grow); `now`: what the layout functions give (exact).  Only the tape differs: the byte formula added
+# 17 x 256 bytes of alignment slack to the sum of the sections and rounded up, the layout rounds each of the 17 sections up to 256
+# bytes by itself (less than 18 x 256 bytes fewer).  The forward workspace still holds the R x 1280 bytes that were once x / P / Q
+# of one step (no kernel is given them; they keep the offsets behind them, see rollout.hip fwd_ws_layout), so the two workspace
+# sizes are the old ones, and the kept-activation buffer is the map CNN's.
+ROLLOUT_BYTES = {
+    'no_edges': dict(sizes=[1, 3], NS=1, FT=1, train=False,
+                     was=(51968, 7128576, 61450752, 256), now=(48128, 7128576, 61450752, 256)),
+    'four_chunks': dict(sizes=[16, 9], NS=1, FT=2, train=False,
+                        was=(1262848, 44187136, 180222464, 44080128), now=(1259264, 44187136, 180222464, 44080128)),
+    'two_tiles': dict(sizes=[19], NS=1, FT=2, train=False,
+                      was=(1077504, 33533440, 146789376, 33500928), now=(1073664, 33533440, 146789376, 33500928)),
+    'two_samples': dict(sizes=[4, 2], NS=2, FT=2, train=False,
+                        was=(313600, 21180416, 106240256, 21158400), now=(309504, 21180416, 106240256, 21158400)),
+    'training': dict(sizes=[4, 2], NS=1, FT=3, train=True,
+                     was=(236288, 10658048, 95590656, 21158400), now=(232704, 10658048, 95590656, 21158400)),
+}
+
+
+@pytest.mark.parametrize('case', sorted(ROLLOUT_BYTES))
+def test_rollout_buffer_sizes_are_pinned(emu, sd, case):
+    """The four size queries of the rollout at the smallest shapes that reach a distinct layout or step plan: a scene without
+    edges; 16 agents = four edge chunks (K workgroups per scene in the forward step, the stepwise reverse sweep); 19 agents = two
+    scene tiles and the launch-per-phase sweep; two samples (no scene kernels, no partial-maxima arrays); the training sweep with
+    kept map-CNN activations (StriveScenes.n_edges set).  The sizes are ABI (callers may cache them): none may grow.  Forward and
+    reverse sweep then run on a tape, a workspace and a kept buffer of EXACTLY the reported bytes, every byte 0xFF, with 0xFF guard
+    bytes behind each: carving must fit what the query reports (an arena that runs out hands the kernels null pointers), nothing
+    may be read before it is written, and nothing written behind the end."""
+    c = ROLLOUT_BYTES[case]
+    sizes, NS, FT, train = c['sizes'], c['NS'], c['FT'], c['train']
+    batch, map_idx, raster, dx = mg.build_inputs(sizes, 'emu', NC=2)
+    env = synth.SyntheticMapEnv(raster, dx)
+    orc = oracle_model(sd)
+    NA = batch.past.shape[0]
+    R = NA * NS
+    dec = params.pack_decoder(sd, 2, env, 'cpu', orc.get_normalizer(), orc.get_att_normalizer(), NUSC_BIKE_PARAMS)
+    sc = params.pack_scenes(batch.ptr, NS, 'cpu')
+    assert sc.struct.n_edges == sum(n * (n - 1) for n in sizes) * NS
+    got = tuple(int(emu.query('strive_rollout_' + q, dec.ref(), sc.ref(), FT))
+                for q in ('tape_bytes', 'workspace_bytes', 'train_workspace_bytes', 'keep_bytes'))
+    print('rollout bytes %s: %r' % (case, got))
+    assert all(g <= w for g, w in zip(got, c['was'])), 'a rollout buffer grew: %r, was %r' % (got, c['was'])
+    assert got == c['now'], 'rollout buffer sizes: %r' % (got,)
+    tb, wb, twb, kb = got
+    GUARD = 4096
+
+    def guarded(nbytes):
+        return torch.full((nbytes + GUARD,), 0xFF, dtype=torch.uint8)
+
+    def intact(buf, nbytes, what):
+        assert bool((buf[nbytes:] == 0xFF).all()), 'the rollout wrote behind its ' + what
+
+    pf = synth.f32(synth.counter_uniform((NA, 64), 'emu/pf', -1, 1))
+    mf = synth.f32(synth.counter_uniform((NA, 64), 'emu/mf', -1, 1))
+    z = synth.f32(synth.counter_uniform((R, 32), 'emu/zz', -1.5, 1.5)).contiguous()
+    rw = synth.f32(synth.counter_uniform((R, FT, 4), 'emu/rw', -1.0, 1.0)).contiguous()
+    mi = map_idx[batch.batch].int().contiguous()
+    lw, sem, past_last = batch.lw.contiguous(), batch.sem.contiguous(), batch.past[:, -1, :].contiguous()
+    nan = float('nan')
+    tape, traj, dz = guarded(tb), torch.full((R, FT, 4), nan), torch.full((R, 32), nan)
+    if not train:
+        ws = guarded(wb)
+        emu.call('strive_rollout_fwd', dec.ref(), sc.ref(), L.ptr(past_last), L.ptr(lw), L.ptr(sem), L.ptr(pf), L.ptr(mf), L.ptr(z),
+                 L.ptr(mi), None, FT, L.ptr(traj), L.ptr(tape), tb, L.ptr(ws), wb, None)
+        intact(ws, wb, 'workspace (forward)')
+        ws.fill_(0xFF)
+        emu.call('strive_rollout_bwd', dec.ref(), sc.ref(), L.ptr(lw), L.ptr(sem), L.ptr(z), None, FT, L.ptr(rw), L.ptr(dz),
+                 L.ptr(tape), tb, L.ptr(ws), wb, None)
+        intact(ws, wb, 'workspace (reverse sweep)')
+        outs = {'traj': traj, 'dz': dz}
+    else:
+        ws, kept = guarded(twb), guarded(kb)
+        emu.call('strive_rollout_fwd_keep', dec.ref(), sc.ref(), L.ptr(past_last), L.ptr(lw), L.ptr(sem), L.ptr(pf), L.ptr(mf),
+                 L.ptr(z), L.ptr(mi), None, FT, L.ptr(traj), L.ptr(tape), tb, L.ptr(ws), wb, L.ptr(kept), kb, None)
+        intact(ws, wb, 'workspace (forward)')
+        intact(kept, kb, 'kept activations')
+        ws.fill_(0xFF)
+        ng, nr, nc = emu.query('strive_gnn_param_count', dec.struct.gnn), emu.query('strive_gru_param_count'), \
+            emu.query('strive_map_cnn_param_count')
+        dpf, dmf = torch.full((NA, 64), nan), torch.full((NA, 64), nan)
+        dg, dr, dcn = torch.zeros(ng), torch.zeros(nr), torch.zeros(nc)        # (weight gradients are accumulated)
+        emu.call('strive_rollout_bwd_train_kept', dec.ref(), sc.ref(), L.ptr(lw), L.ptr(sem), L.ptr(z), None, L.ptr(mi), FT, L.ptr(rw),
+                 L.ptr(dz), L.ptr(dpf), L.ptr(dmf), L.ptr(dg), L.ptr(dr), L.ptr(dcn), L.ptr(tape), tb, L.ptr(kept), kb, L.ptr(ws), twb,
+                 None)
+        intact(ws, twb, 'training workspace')
+        intact(kept, kb, 'kept activations (reverse sweep)')
+        outs = {'traj': traj, 'dz': dz, 'd past_feat': dpf, 'd map_feat': dmf, 'd decoder_net': dg, 'd decoder_memory': dr,
+                'd map CNN': dcn}
+    intact(tape, tb, 'tape')
+    for name, t in outs.items():
+        assert torch.isfinite(t).all() and float(t.abs().max()) > 0.0, name
+
+
 def _adv_quarantine_case(dead, key='emu/quarantine', sizes=(3, 5, 2, 4), D=32):
     """a ragged batch, the same batch without the scenes in ``dead``, and the row maps between them"""
     batch, map_idx, env, traj, veh_att = _loss_case(list(sizes), key)
