@@ -443,8 +443,10 @@ class AdvGenLoss(nn.Module):
         mx = torch.full((self.B,), float('-inf'), device=din.device).scatter_reduce(0, seg.reshape(-1), neg.reshape(-1),
                                                                                     reduce='amax', include_self=True)
         e = torch.exp(neg - mx[self.seg].view(-1, 1))
-        den = torch.zeros((self.B,), device=din.device).scatter_add(0, seg.reshape(-1), e.reshape(-1))
-        soft = e / den[self.seg].view(-1, 1)
+        # the denominator in float64 like adv_crash_kernel's: scatter_add adds a scene's entries one after the other, and an fp32
+        # sum of 1000 of them is 5e-6 off (64 agents x 16 steps), which every weight and gradient of the scene inherits
+        den = torch.zeros((self.B,), dtype=torch.float64, device=din.device).scatter_add(0, seg.reshape(-1), e.reshape(-1).double())
+        soft = (e.double() / den[self.seg].view(-1, 1)).to(e.dtype)
         return torch.where(torch.isnan(soft), torch.zeros_like(soft), soft)
 
     def _setup(self):
