@@ -883,6 +883,21 @@ int strive_dataset_gather_batch(const StriveSceneTables* tb, const int32_t* seq,
                                 float* future_vis, int64_t* batch, int64_t* map_idx, int64_t* edge_index, int64_t E,
                                 strive_stream_t stream);
 
+/* One Adam step of the training loop (reference src/train_traffic.py:275-277 creates optim.Adam(model.parameters(), lr,
+ * weight_decay), :113-115 steps it) over ALL parameters at once, in one kernel launch: p, g, m (exp_avg), v (exp_avg_sq) are flat
+ * fp32 arrays of n elements, 16-byte aligned -- the unpadded concatenation of the parameter tensors in model.parameters() order.
+ * Per element, in fp32, the arithmetic of torch.optim.Adam's single-tensor form (amsgrad and maximize off):
+ *   g' = g + weight_decay p;  m += (g' - m)(1 - beta1);  v = beta2 v + (1 - beta2) g' g';
+ *   p -= (lr / bc1) m / (sqrt(v) / sqrt(bc2) + eps)
+ * with bc1 = 1 - beta1^t and bc2 = 1 - beta2^t formed by the host in double.  p, m, v are updated in place, g is only read.
+ * seg_off (nseg + 1 int64 on the device, seg_off[0] = 0 <= ... <= seg_off[nseg] = n) names the tensors; if seg_absmax != NULL the
+ * same pass writes seg_absmax[s] = max |p_new| over segment s (nseg floats; 0 for an empty segment, NaN if the segment holds a NaN):
+ * exact and independent of the order of execution (an integer maximum of the bit patterns).  The table need not be cleared by the
+ * caller.  seg_off and nseg are ignored when seg_absmax is NULL. */
+int strive_adam_flat(float* p, const float* g, float* m, float* v, int64_t n, double lr, double beta1, double beta2, double eps,
+                     double weight_decay, double bc1, double bc2, const int64_t* seg_off, int32_t nseg, float* seg_absmax,
+                     strive_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

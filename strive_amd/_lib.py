@@ -234,6 +234,8 @@ PROTOTYPES = {
     'strive_dataset_window_counts': (C.c_int, [C.POINTER(StriveSceneTables), P, I, I, I, I, P, P]),
     'strive_dataset_gather_batch': (C.c_int, [C.POINTER(StriveSceneTables), P, P, I, I, I, I, I, C.POINTER(StriveNorm), P, P, P, P, P, P,
                                               P, P, P, P, P, C.c_int64, P]),
+    'strive_adam_flat': (C.c_int, [P, P, P, P, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
+                                   C.c_double, P, I, P, P]),
 }
 
 

@@ -113,6 +113,14 @@ class DataParallelTrainer(object):
             n = p.numel()
             self._views.append(self.bucket[off:off + n].view_as(p))
             off += n
+        # a FlatAdam (optim.py) reads the gradients from the bucket itself -- the layouts are the same, one buffer serves both, the
+        # vote slot behind the gradients is not its business -- and announces its parameter update itself
+        from .optim import FlatAdam
+        self._flat_optim = isinstance(optimizer, FlatAdam)
+        if self._flat_optim:
+            if [id(p) for p in optimizer.flat_params] != [id(p) for p in self.params]:
+                raise ValueError('the FlatAdam optimiser must hold exactly the model\'s trainable parameters, in model.parameters() order')
+            optimizer.use_grad_buffer(self.bucket)
 
     def _bind_grads(self):
         for p, v in zip(self.params, self._views):
@@ -204,8 +212,10 @@ class DataParallelTrainer(object):
         if any_failed:
             return None                    # this rank or another one failed: nobody steps
         self.optimizer.step()
-        # (fused optimisers update the parameters without bumping their version counters, which the pack caches key on)
-        params.parameters_changed()
+        # (fused optimisers update the parameters without bumping their version counters, which the pack caches key on; a FlatAdam
+        #  has announced its step itself, so that the max |w| table the step wrote counts as current: params._table_norms)
+        if not self._flat_optim:
+            params.parameters_changed()
         out = dict(loss_dict)
         out['global_loss'] = self._all_reduce(share.detach().clone().reshape(1))
         return out

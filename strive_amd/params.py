@@ -94,13 +94,50 @@ def _lag_key(t):
     return (t.data_ptr(), tuple(t.shape), str(t.device))
 
 
+# Max |w| from an optimiser that writes it.  FlatAdam (optim.py) keeps the parameters as views of one flat buffer and its step leaves
+# max |w| of every tensor in a device table; while that table is CURRENT -- no parameter update announced since the step that wrote
+# it (the step announces itself), no in-place operation on the tensor since -- the values both prefetch paths below need are one
+# index_select of the table instead of _foreach_norm + stack over the tensors.  The maximum is exact, so the values are the same.
+# STRIVE_ABSMAX_TABLE=0 switches the source off (A/B runs, tests).
+_SOURCES = []         # weak references to the registered optimisers
+
+
+def register_absmax_source(opt):
+    import weakref
+    _SOURCES[:] = [r for r in _SOURCES if r() is not None and r() is not opt] + [weakref.ref(opt)]
+
+
+def _table_norms(todo, keys):
+    """(len(todo),) device tensor of max |t| gathered from ONE registered optimiser's current table, or None if any tensor is not
+    served (not a registered view, table not current, tensor touched since)."""
+    if not _SOURCES or os.environ.get('STRIVE_ABSMAX_TABLE', '1') == '0':
+        return None
+    for r in _SOURCES:
+        opt = r()
+        if opt is None or opt.table_epoch != _PARAM_EPOCH[0]:
+            continue
+        rows = opt.absmax_rows()
+        idx = [rows.get(k) for k in keys]
+        if any(i is None for i in idx) or not all(opt.absmax_current(i, t) for i, t in zip(idx, todo)):
+            continue
+        return opt.absmax_table.index_select(0, opt.absmax_index(tuple(keys), idx))
+    return None
+
+
+def _norms(todo, keys):
+    tab = _table_norms(todo, keys)
+    if tab is not None:
+        return tab
+    return torch.stack(torch._foreach_norm([t.to(torch.float32) for t in todo], float('inf')))
+
+
 def _lagged_prefetch(tensors, slack):
     todo = [t.detach() for t in tensors if t.numel() > 0 and _absmax_key(t.detach()) not in _ABSMAX]
     if not todo:
         return
     dev = todo[0].device
     if dev.type != 'cuda':
-        vals = torch.stack(torch._foreach_norm([t.to(torch.float32) for t in todo], float('inf'))).tolist()
+        vals = _norms(todo, [_lag_key(t) for t in todo]).tolist()
         for t, v in zip(todo, vals):
             _ABSMAX[_absmax_key(t)] = (float(v), t)
         return
@@ -108,7 +145,7 @@ def _lagged_prefetch(tensors, slack):
     group = tuple(keys)
     fifo = _LAG_BATCH.setdefault(group, [])
     # enqueue this call's read-back
-    norms = torch.stack(torch._foreach_norm([t.to(torch.float32) for t in todo], float('inf')))
+    norms = _norms(todo, keys)
     host = torch.empty((len(todo),), dtype=torch.float32).pin_memory()
     host.copy_(norms, non_blocking=True)
     ev = torch.cuda.Event()
@@ -154,7 +191,7 @@ def prefetch_absmax(tensors):
         return
     if len(_ABSMAX) + len(todo) > 2048:
         _ABSMAX.clear()
-    vals = torch.stack(torch._foreach_norm([t.to(torch.float32) for t in todo], float('inf'))).tolist()
+    vals = _norms(todo, [_lag_key(t) for t in todo]).tolist()
     for k, v, t in zip(keys, vals, todo):
         _ABSMAX[k] = (float(v), t)
 

@@ -1,0 +1,361 @@
+"""Training of the traffic model (reference src/train_traffic.py:25-364) on the scene dataset of a tracks file:
+
+    python -m strive_amd.train_traffic --tracks TRAIN --val_tracks VAL --out OUT [--config FILE] [--ckpt CKPT]
+
+writes ``OUT/train_log.txt`` and the reference's checkpoints (``OUT/checkpoints/best_eval_model.pth``, ``epoch_%08d_model.pth``,
+``latest_model.pth``: ``save_state`` files that ``eval_traffic_tracks`` and the reference's ``load_state`` read).  The arguments are
+the reference's, with its defaults; its ``split='train' / 'val'`` of the devkit's tables become two tracks files (datasets/tracks.py;
+no ``--val_tracks``: no validation).  Maps come from ``synth.make_raster`` as in ``eval_traffic_tracks.tracks_loader``.  Rendering
+and wandb are not offered; single process only.
+
+Differences in HOW, not in what is computed:
+
+* A training batch is one ``DataParallelTrainer.step`` (distributed.py): forward, ``TrafficModelLoss``, backward straight into the
+  flat gradient bucket, optimiser step.  With ``--optim flat`` the optimiser is ``FlatAdam`` (optim.py: the Adam step and max |w| of
+  every tensor in one launch); ``--optim torch`` is ``torch.optim.Adam`` as in the reference.  Checkpoints of either resume with
+  the other.
+* Per-batch loss and error terms stay on the device in float64 (sum, count) accumulators and are read back once per epoch (and,
+  for the running means of a log line, every ``print_every`` batches).  The epoch means are the reference's: the mean over all
+  concatenated elements of a key, not a mean of batch means.
+"""
+import os
+import time
+
+import torch
+
+from . import test_traffic as TT
+from .losses.common import log_normal
+
+DEVKIT_KEYS = ('data_dir', 'data_version', 'num_workers', 'map_layers', 'wandb_project', 'wandb_name', 'wandb_offline')
+DEFAULT_OPTIM = 'flat'
+
+
+# name, type, default, what it is -- the reference's argument names and defaults (its src/train_traffic.py:35-54 and the base arguments it
+# uses); lists are nargs='+'
+ARGUMENTS = (
+    ('out', str, './out/traffic_out', 'where train_log.txt and checkpoints/ go'),
+    ('ckpt', str, None, 'a save_state file to resume from: weights, optimiser state, epoch and best validation loss'),
+    ('batch_size', int, 4, 'windows per batch'),
+    ('past_len', int, 4, 'observed frames per window'),
+    ('future_len', int, 12, 'predicted frames per window'),
+    ('map_obs_size_pix', int, 256, 'side of the square map crop around an agent, in pixels'),
+    ('latent_size', int, 32, 'width of the latent z'),
+    ('agent_types', [str], None, 'the agent categories; must be the category set that has normalisation statistics for their number '
+                                 '(default: that set for --num_classes)'),
+    ('num_classes', int, 2, 'number of agent categories when --agent_types is not given'),
+    ('tracks', str, None, 'tracks file (datasets/tracks.py) to train on'),
+    ('val_tracks', str, None, 'tracks file to validate on; leave out to train without validation'),
+    ('scenario_dir', str, None, 'directory of scenario files appended to the training windows'),
+    ('data_noise_std', float, 0.0, 'sigma of the Gaussian noise on the observed states of training batches'),
+    ('epochs', int, 200, 'index of the last epoch + 1'),
+    ('val_every', int, 3, 'validate in every epoch divisible by this'),
+    ('save_every', int, 3, 'write epoch_N and latest checkpoints in every epoch divisible by this'),
+    ('print_every', int, 10, 'log running means after every so many batches (0: never; each costs one read-back)'),
+    ('lr', float, 1e-5, 'Adam step size'),
+    ('weight_decay', float, 0.0, 'L2 coefficient added to the gradients'),
+    ('loss_kl', float, 0.004, 'weight of the KL term once annealing has ended'),
+    ('kl_anneal_end', int, 20, 'epoch at which the linearly growing KL weight reaches --loss_kl; best-loss tracking restarts there'),
+    ('loss_recon', float, 1.0, 'weight of the reconstruction term'),
+    ('loss_veh_coll_prior', float, 0.05, 'weight of the vehicle-collision penalty on a prior sample'),
+    ('loss_env_coll_prior', float, 0.1, 'weight of the off-road penalty on a prior sample'),
+    ('device', str, 'cuda:0', 'torch device of model, data and maps'),
+    ('seed', int, 0, 'seeds the shuffle, the data noise, the initial weights and the latent draws'),
+)
+
+
+def get_parser():
+    import argparse
+    p = argparse.ArgumentParser(description='Train the traffic model on tracks files')
+    p.add_argument('-c', '--config', type=str, default=None, help='file of `key: value` lines; the command line wins over it')
+    for name, kind, default, text in ARGUMENTS:
+        if isinstance(kind, list):
+            p.add_argument('--' + name, type=kind[0], nargs='+', default=default, help=text)
+        else:
+            p.add_argument('--' + name, type=kind, default=default, help=text)
+    p.add_argument('--optim', type=str, default=DEFAULT_OPTIM, choices=['flat', 'torch'],
+                   help='flat: FlatAdam, the whole step in one launch; torch: torch.optim.Adam')
+    return p
+
+
+def read_config(path):
+    """The reference's .cfg shape: flat ``key: value`` lines, ``#`` comments.  Returns [(key, value string)] in file order."""
+    out = []
+    with open(path) as f:
+        for no, line in enumerate(f, 1):
+            line = line.split('#', 1)[0].strip()
+            if not line:
+                continue
+            if ':' not in line:
+                raise ValueError('%s:%d: expected `key: value`' % (path, no))
+            k, v = line.split(':', 1)
+            out.append((k.strip(), v.strip()))
+    return out
+
+
+def parse_cfg(argv=None, log=None):
+    """Defaults < ``--config`` file < command line.  An unknown key in the file is an error; the keys that describe the devkit's data
+    (DEVKIT_KEYS) are accepted and ignored with one log line.  Returns the config dict and the ignored keys."""
+    p = get_parser()
+    pre, _ = p.parse_known_args(argv)
+    ignored = []
+    if pre.config is not None:
+        known = {a.dest: a for a in p._actions}
+        file_args = []
+        for k, v in read_config(pre.config):
+            if k in DEVKIT_KEYS:
+                ignored.append(k)
+                continue
+            if k not in known or k in ('config', 'help'):
+                raise ValueError('%s: unknown key `%s`' % (pre.config, k))
+            v = v.strip()
+            if v[:1] == '[' and v[-1:] == ']':                 # a YAML list: [a, b]
+                v = ' '.join(s.strip().strip('\'"') for s in v[1:-1].split(','))
+            file_args += ['--' + k] + (v.split() if known[k].nargs in ('+', '*') or isinstance(known[k].nargs, int) else [v.strip('\'"')])
+        argv_all = file_args + list(argv if argv is not None else __import__('sys').argv[1:])
+        cfg = vars(p.parse_args(argv_all))
+    else:
+        cfg = vars(p.parse_args(argv))
+    if cfg['agent_types'] is not None:
+        cfg['num_classes'] = len(cfg['agent_types'])
+    return cfg, ignored
+
+
+def _move(obj, device):
+    if torch.is_tensor(obj) or hasattr(obj, 'keys'):
+        return TT._to_device(obj, device, keep=('ptr', 'edge_index'))
+    return (obj.to(device) if hasattr(obj, 'to') else obj), {}
+
+
+def _err_terms(loss_fn, scene_graph, pred, normalizer):
+    """``loss_fn.compute_err`` (reference src/losses/traffic_model.py:120-164).  For TrafficModelLoss the same terms without the
+    boolean-mask compaction (a read-back per batch): pos_err / ang_err dense, (NA,T), beside the mask of the visible frames."""
+    from .losses.traffic_model import TrafficModelLoss
+    if not isinstance(loss_fn, TrafficModelLoss):
+        return loss_fn.compute_err(scene_graph, pred, normalizer), {}
+    vis = scene_graph.future_vis == 1.0
+    gt = normalizer.unnormalize(scene_graph.future_gt)
+    pf = normalizer.unnormalize(pred['future_pred'])
+    pos_err = torch.norm(gt[..., :2] - pf[..., :2], dim=-1)
+    gh = gt[..., 2:4] / torch.norm(gt[..., 2:4], dim=-1, keepdim=True)
+    ph = pf[..., 2:4] / torch.norm(pf[..., 2:4], dim=-1, keepdim=True)
+    ang_err = torch.rad2deg(torch.acos(torch.sum(gh * ph, dim=-1).clamp(-1, 1)))
+    pm, pv = pred['prior_out']
+    qm = pred['posterior_out'][0]
+    return ({'pos_err': pos_err, 'ang_err': ang_err, 'z_logprob': log_normal(qm, pm, pv),
+             'z_mdist': torch.norm((qm - pm) / torch.sqrt(pv), dim=-1)}, {'pos_err': vis, 'ang_err': vis})
+
+
+def _trainer_for(model, loss_fn, optimizer):
+    """The DataParallelTrainer of (model, loss_fn, optimizer): kept on the optimiser, it owns the flat gradient bucket"""
+    from .distributed import DataParallelTrainer
+    ent = optimizer.__dict__.get('_strive_trainer')
+    if ent is None or ent[0] is not model or ent[1] is not loss_fn:
+        ent = (model, loss_fn, DataParallelTrainer(model, loss_fn, optimizer))
+        optimizer.__dict__['_strive_trainer'] = ent
+    return ent[2]
+
+
+def run_one_epoch(data_loader, model, map_env, loss_fn, device, out_path, train=True, optimizer=None, step_counter=0, log=None,
+                  print_every=0):
+    """Run through ``data_loader`` -- any iterable of ``(scene_graph, map_idx)`` -- for one epoch; trains if desired (reference
+    src/train_traffic.py:64-171).  Returns ``(step_counter, mean_epoch_loss)``; ``step_counter`` advances by the number of scenes of
+    every training batch that was stepped.  A ``RuntimeError`` in a batch is logged and the batch skipped."""
+    if train and optimizer is None:
+        raise ValueError('Must give optimizer to train!')
+    prefix = 'Train' if train else 'Eval'
+    device = torch.device(device)
+    acc = TT._Accumulators(device)
+    trainer = _trainer_for(model, loss_fn, optimizer) if train else None
+    captured = {}
+    hook = model.register_forward_hook(lambda mod, inp, out: captured.__setitem__('pred', out)) if train else None
+    nbatch = 0
+    try:
+        for i, (scene_graph, map_idx) in enumerate(data_loader):
+            try:
+                scene_graph, host = _move(scene_graph, device)
+                map_idx, _ = _move(map_idx, device)
+                if host.get('ptr') is not None and '_strive_scene_info' not in scene_graph.__dict__:
+                    from . import ops
+                    ops.prime_scene_info(scene_graph, host['ptr'], host.get('edge_index'))
+                B = int(map_idx.size(0))
+                w = loss_fn.loss_weights
+                want_sample = w['coll_veh_prior'] > 0.0 or w['coll_env_prior'] > 0.0
+                if train:
+                    captured.clear()
+                    loss_dict = trainer.step(scene_graph, map_idx, map_env, future_sample=want_sample)
+                    if loss_dict is None:
+                        raise trainer.last_error
+                    loss_dict = {k: v for k, v in loss_dict.items() if k != 'global_loss'}
+                    pred = captured['pred']
+                else:
+                    with torch.no_grad():
+                        pred = model(scene_graph, map_idx, map_env, future_sample=want_sample)
+                        loss_dict = loss_fn(scene_graph, pred, map_idx=map_idx, map_env=map_env)
+            except RuntimeError as err:                       # the reference skips such a batch (out of memory, mostly) and goes on
+                for line in ('Caught error in training batch %s!' % err, 'Skipping'):
+                    TT._log(log, line)
+                captured.clear()
+                continue
+            if train:
+                step_counter += B              # the optimiser has stepped: whatever follows, the batch counts
+            with torch.no_grad():
+                err_dict, err_masks = _err_terms(loss_fn, scene_graph, pred, model.get_normalizer())
+            for terms in (loss_dict, err_dict):               # the reference's key order: loss terms, then error terms
+                for key, values in terms.items():
+                    if values is not None:
+                        acc.add(key, values, err_masks.get(key))
+            nbatch += 1
+            if print_every and nbatch % print_every == 0:
+                means = _read_means(acc)
+                TT._log(log, '%s batch %d: %s' % (prefix, i, ', '.join('%s %f' % kv for kv in means.items())))
+    finally:
+        if hook is not None:
+            hook.remove()
+    means = _read_means(acc)
+    for k, v in means.items():
+        TT._log(log, '%s Epoch Mean %s = %f' % (prefix, k, v))
+    return step_counter, means.get('loss', float('nan'))
+
+
+def _read_means(acc):
+    """the one read-back: {key: sum / count} of every accumulator"""
+    keys = list(acc.sums.keys())
+    if not keys:
+        return {}
+    vals = torch.stack([acc.sums[k] for k in keys] + [acc.counts[k].to(torch.float64) for k in keys]).cpu().tolist()
+    n = len(keys)
+    return {k: (vals[i] / vals[n + i] if vals[n + i] > 0 else float('nan')) for i, k in enumerate(keys)}
+
+
+def make_optimizer(kind, model, lr, weight_decay):
+    if kind == 'flat':
+        from .optim import FlatAdam
+        return FlatAdam(model.parameters(), lr=lr, weight_decay=weight_decay)
+    return torch.optim.Adam(model.parameters(), lr=lr, weight_decay=weight_decay)
+
+
+def epoch_plan(epoch, cfg, has_val):
+    """What epoch ``epoch`` does besides training, as the reference schedules it (src/train_traffic.py:309-357): the KL weight it
+    trains with (None: no annealing), whether best-loss tracking restarts, whether it validates and whether it writes the
+    periodic checkpoints."""
+    end = cfg['kl_anneal_end']
+    from .utils.torch import compute_kl_weight
+    return {'kl': None if end is None else compute_kl_weight(epoch, end, cfg['loss_kl']),
+            'restart_best': end is not None and epoch == end,
+            'validate': has_val and epoch % cfg['val_every'] == 0,
+            'save': epoch % cfg['save_every'] == 0}
+
+
+def train_loop(cfg, model, loss_fn, optimizer, train_loader, val_loader, map_env, val_map_env, device, log, ckpt_epoch=0,
+               ckpt_eval_loss=float('inf')):
+    """Epochs ``ckpt_epoch .. cfg['epochs'] - 1``, each as ``epoch_plan`` says.  A resumed run starts AT the checkpoint's epoch, as
+    the reference does: that epoch is trained again and its ``epoch_N`` file rewritten.  Returns (step counter, best loss)."""
+    from .utils.torch import save_state
+    folder = os.path.join(cfg['out'], 'checkpoints')
+    os.makedirs(folder, exist_ok=True)
+
+    def checkpoint(name, epoch, best):
+        save_state(os.path.join(folder, name), model, optimizer, cur_epoch=epoch, min_val_loss=best)
+    if cfg['kl_anneal_end'] is not None:
+        if cfg['kl_anneal_end'] <= 0:
+            raise ValueError('kl_anneal_end must be positive')
+        TT._log(log, 'Using KL annealing...')
+    seen, best = 0, ckpt_eval_loss
+    for epoch in range(ckpt_epoch, cfg['epochs']):
+        plan = epoch_plan(epoch, cfg, val_loader is not None)
+        TT._log(log, 'Starting epoch %d...' % epoch)
+        if plan['kl'] is not None:
+            loss_fn.loss_weights['kl'] = plan['kl']
+            TT._log(log, 'KL weight %f...' % plan['kl'])
+        if plan['restart_best']:
+            TT._log(log, 'KL ANNEALING FINISHED: resetting val loss tracking...')
+            best = float('inf')
+        t0 = time.time()
+        model.train()
+        seen, _ = run_one_epoch(train_loader, model, map_env, loss_fn, device, cfg['out'], train=True, optimizer=optimizer,
+                                step_counter=seen, log=log, print_every=cfg.get('print_every', 0))
+        TT._log(log, 'Epoch time: %f' % (time.time() - t0))
+        if plan['validate']:
+            TT._log(log, 'Validating...')
+            model.eval()
+            seen, val_loss = run_one_epoch(val_loader, model, val_map_env, loss_fn, device, cfg['out'], train=False, step_counter=seen,
+                                           log=log)
+            if val_loss < best:
+                best = val_loss
+                TT._log(log, 'Lowest eval loss so far! Saving checkpoint...')
+                checkpoint('best_eval_model.pth', epoch, best)
+        if plan['save']:
+            TT._log(log, 'Saving checkpoint...')
+            checkpoint('epoch_%08d_model.pth' % epoch, epoch, best)
+            checkpoint('latest_model.pth', epoch, best)
+    return seen, best
+
+
+def categories_for(cfg):
+    """The category set of the run: the one set that has normalisation statistics for ``num_classes`` categories (what
+    eval_traffic_tracks.tracks_loader picks); ``--agent_types`` must name exactly that set."""
+    from .datasets.utils import NUSC_NORM_STATS
+    by_count = {len(k): list(k) for k in NUSC_NORM_STATS}
+    if cfg['num_classes'] not in by_count:
+        raise SystemExit('normalisation statistics exist for %s categories, not for %d' % (sorted(by_count), cfg['num_classes']))
+    cats = by_count[cfg['num_classes']]
+    if cfg['agent_types'] is not None and sorted(cfg['agent_types']) != sorted(cats):
+        raise SystemExit('--agent_types %s: the category set with normalisation statistics for %d categories is %s' % (
+            ' '.join(cfg['agent_types']), cfg['num_classes'], ' '.join(cats)))
+    return cats
+
+
+def open_data(cfg, device):
+    """(training loader, its maps, validation loader or None, its maps) from the tracks files of ``cfg``"""
+    from .eval_traffic_tracks import tracks_loader
+    shape = {k: cfg[k] for k in ('num_classes', 'past_len', 'future_len', 'batch_size')}
+    plain, maps = tracks_loader(dict(shape, tracks=cfg['tracks'], scenario_path=cfg['scenario_dir']), device)
+    ds = plain.dataset
+    ds.noise_std = cfg['data_noise_std']
+    shuffled = ds.loader(cfg['batch_size'], shuffle=True, generator=torch.Generator().manual_seed(cfg['seed']))
+    if cfg['val_tracks'] is None:
+        return shuffled, maps, None, None
+    return (shuffled, maps) + tuple(tracks_loader(dict(shape, tracks=cfg['val_tracks'], scenario_path=None), device))
+
+
+def main(argv=None):
+    from .constants import NUSC_BIKE_PARAMS
+    from .losses.traffic_model import TrafficModelLoss
+    from .models.traffic_model import TrafficModel
+    from .utils.torch import count_params, load_state
+    cfg, ignored = parse_cfg(argv)
+    if cfg['tracks'] is None and cfg['scenario_dir'] is None:
+        raise SystemExit('train_traffic needs --tracks FILE (and / or --scenario_dir DIR)')
+    categories_for(cfg)
+    os.makedirs(cfg['out'], exist_ok=True)
+    resuming = cfg['ckpt'] is not None
+    with open(os.path.join(cfg['out'], 'train_log.txt'), 'a' if resuming else 'w') as log:
+        TT._log(log, 'Args: ' + str(cfg))
+        if ignored:
+            TT._log(log, 'Ignoring config keys that describe the devkit\'s data: ' + ', '.join(ignored))
+        device = torch.device(cfg['device'])
+        TT._log(log, 'Using device %s...' % str(device))
+        torch.manual_seed(cfg['seed'])
+        train_loader, map_env, val_loader, val_map_env = open_data(cfg, device)
+        data = train_loader.dataset
+        state_norm, att_norm = data.get_state_normalizer(), data.get_att_normalizer()
+        model = TrafficModel(cfg['past_len'], cfg['future_len'], cfg['map_obs_size_pix'], len(data.categories),
+                             latent_size=cfg['latent_size']).to(device)
+        TT._log(log, 'Num model params: %d' % count_params(model))
+        weights = {'recon': cfg['loss_recon'], 'kl': cfg['loss_kl'], 'coll_veh_prior': cfg['loss_veh_coll_prior'],
+                   'coll_env_prior': cfg['loss_env_coll_prior']}
+        loss_fn = TrafficModelLoss(weights, state_norm, att_norm).to(device)
+        optimizer = make_optimizer(cfg['optim'], model, cfg['lr'], cfg['weight_decay'])     # (after .to(device): FlatAdam re-points p.data)
+        start, best = 0, float('inf')
+        if resuming:
+            start, best = load_state(cfg['ckpt'], model, optimizer=optimizer, map_location=device)
+            TT._log(log, 'Loaded checkpoint from epoch %d with validation loss %f...' % (start, best))
+        model.set_normalizer(state_norm)                     # (after the load: the run's statistics are the training dataset's)
+        model.set_att_normalizer(att_norm)
+        model.set_bicycle_params(NUSC_BIKE_PARAMS)
+        return train_loop(cfg, model, loss_fn, optimizer, train_loader, val_loader, map_env, val_map_env, device, log,
+                          ckpt_epoch=start, ckpt_eval_loss=best)
+
+
+if __name__ == '__main__':
+    main()
