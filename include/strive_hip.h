@@ -542,6 +542,29 @@ int strive_traffic_eval_metrics(const float* pred, const float* gt, const float*
                                 int32_t T, int32_t Tg, double* pos_err, double* ang_err, double* disp, int32_t* did_veh,
                                 int32_t* did_map, int32_t* grid_i, double* grid_d, int32_t* status, strive_stream_t stream);
 
+/* Collision verdicts of the refine driver (compute_metrics, reference src/refine_traffic_optim.py:84-121, with
+ * check_pairwise_veh_coll of reference src/losses/adv_gen_nusc.py:567-623 and compute_coll_rate_env of reference
+ * src/losses/traffic_model.py:366-419 -> check_on_layer, reference src/datasets/nuscenes_utils.py:266-298) for B scenes in one
+ * host call without a host synchronisation, each scene as if compute_metrics had been called on that scene alone: two
+ * launches, float64 on the fp32 inputs, any scene size.
+ *   traj (NA,T,4) and lw (NA,2) NORMALISED, unnormalised in fp32 as for strive_traffic_eval_metrics with the four host arrays;
+ *   ptr (B+1) agent offsets; map + mapix (B) + lin_tab / lin_max as for strive_scenario_eval_metrics.
+ *   did_veh (NA) int32: agent i overlaps (IoU > 0.02) an agent j > i of its scene at some step; NaN frames never hit
+ *   did_env (NA) int32: some valid frame has fp32(count) / fp32(L W) < fp32(0.95) on raster layer 0, the grid L = round(mean_l /
+ *         mean(dx)), W likewise, formed from the valid (agent, step) rows of THAT SCENE (mean(dx) over all entries of the
+ *         map's dx); a scene without a valid row has L = W = 0, NaN ratios and no environment collision
+ *   out_i (B,8) int32 : num_coll_veh, num_traj_veh (= n), env_coll, env_total (= n), success (both counts 0), L, W, valid rows
+ *   grid_d (B,2)      : the two ratios before rounding
+ *   status (B) int32  : 0 = written; 2 = offsets leave the arrays or n < 1; 3 = map index out of range; 4 = this scene's grid
+ *         is outside 1..lin_max (other scenes are unaffected).  Every output of a scene with a non-zero status is untouched.
+ * No floating-point atomics and every sum in a fixed order: a scene's outputs are bit-identical whatever else is in the batch
+ * and however many workgroups serve the scene. */
+int strive_refine_verdicts(const float* traj, const int32_t* ptr, const float* lw, const float* state_mean4_host,
+                           const float* state_std4_host, const float* att_mean2_host, const float* att_std2_host,
+                           const StriveMap* map, const int32_t* mapix, const float* lin_tab, int32_t lin_max, int32_t B,
+                           int32_t NA, int32_t T, int32_t* did_veh, int32_t* did_env, int32_t* out_i, double* grid_d,
+                           int32_t* status, strive_stream_t stream);
+
 /* One Lloyd step of k-means on x (N,F) float64 with centers (k,F), F = 1..8, k = 1..64 (the clustering of reference
  * src/cluster_scenarios.py, which calls scikit-learn's KMeans on the host): labels (N) = nearest centre, the lowest index on
  * equal squared distance; mind (N) that distance; sums (k,F) and counts (k) per cluster; inertia (1) = sum of mind.  Two

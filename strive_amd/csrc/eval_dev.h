@@ -87,6 +87,18 @@ __device__ __forceinline__ bool boxes_hit(const PA* a, const float* lwa, const P
     return !nan4(a) && !nan4(b) && box_iou(a, lwa, b, lwb) > EVAL_IOU_THRESH;
 }
 
+// A reject before the clip: the centres lie further apart than the two half-diagonals together, so the boxes share no point and
+// their IoU is 0.  Exact as a decision on IoU > EVAL_IOU_THRESH: where rounding could turn this comparison the boxes touch at
+// most at a corner.  false for a NaN anywhere (the clip decides).
+template <typename PA, typename PB>
+__device__ __forceinline__ bool boxes_apart(const PA* a, const float* lwa, const PB* b, const float* lwb) {
+#pragma clang fp contract(off)
+    const double dx = (double)a[0] - (double)b[0], dy = (double)a[1] - (double)b[1];
+    const double la = (double)lwa[0], wa = (double)lwa[1], lb = (double)lwb[0], wb = (double)lwb[1];
+    const double r = 0.5 * (sqrt(la * la + wa * wa) + sqrt(lb * lb + wb * wb));
+    return dx * dx + dy * dy > r * r;
+}
+
 // One fine frame j of interp_traj (reference src/losses/adv_gen_nusc.py:625-644) of the trajectory tr (T, 4) up-sampled by
 // 1 / rs: half-pixel linear taps as ATen's area_pixel_compute_source_index evaluates them in the tensor's type S, heading
 // renormalised.  A NaN tap gives a NaN frame.

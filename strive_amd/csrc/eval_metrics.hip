@@ -537,13 +537,36 @@ struct TrafficEvalArgs {
     int32_t* grid_i; double* grid_d; int32_t* status;
 };
 
-__device__ __forceinline__ void te_pose(const TrafficEvalArgs& A, const float* p, float u[4]) {
+// (Args: TrafficEvalArgs or RefineVerdictArgs -- both hold the normaliser statistics sm, ss, am, asd and the sizes lw)
+template <typename Args>
+__device__ __forceinline__ void te_pose(const Args& A, const float* p, float u[4]) {
     for (int c = 0; c < 4; ++c) u[c] = unnorm1(p[c], A.sm[c], A.ss[c]);
 }
 
-__device__ __forceinline__ void te_lw(const TrafficEvalArgs& A, int ag, float u[2]) {
+template <typename Args>
+__device__ __forceinline__ void te_lw(const Args& A, int ag, float u[2]) {
     u[0] = unnorm1(A.lw[(size_t)ag * 2 + 0], A.am[0], A.asd[0]);
     u[1] = unnorm1(A.lw[(size_t)ag * 2 + 1], A.am[1], A.asd[1]);
+}
+
+// The valid-row count and the two size sums of a sampling grid from the TE_NT per-thread partials: thread 0 adds them in thread
+// order (the totals are valid in thread 0 only; holds a barrier, so the whole workgroup calls it).
+__device__ __forceinline__ void te_row_sums(int tid, long long cnt, double sl, double sw, long long* s_cnt, double* s_l, double* s_w,
+                                            long long& tot, double& tl, double& tw) {
+#pragma clang fp contract(off)
+    s_cnt[tid] = cnt;
+    s_l[tid] = sl;
+    s_w[tid] = sw;
+    __syncthreads();
+    tot = 0;
+    tl = 0.0;
+    tw = 0.0;
+    if (tid != 0) return;
+    for (int i = 0; i < TE_NT; ++i) {
+        tot += s_cnt[i];
+        tl += s_l[i];
+        tw += s_w[i];
+    }
 }
 
 // torch.min over values that may hold NaN: NaN wins
@@ -580,18 +603,10 @@ __global__ __launch_bounds__(TE_NT) void traffic_eval_grid_kernel(TrafficEvalArg
             sw += (double)c * (double)lwu[1];
         }
     }
-    s_cnt[tid] = cnt;
-    s_l[tid] = sl;
-    s_w[tid] = sw;
-    __syncthreads();
+    long long tot;
+    double tl, tw;
+    te_row_sums(tid, cnt, sl, sw, s_cnt, s_l, s_w, tot, tl, tw);
     if (tid != 0) return;
-    long long tot = 0;
-    double tl = 0.0, tw = 0.0;
-    for (int i = 0; i < TE_NT; ++i) {
-        tot += s_cnt[i];
-        tl += s_l[i];
-        tw += s_w[i];
-    }
     double mean[2], ratio[2] = {eval_nan(), eval_nan()};
     int L = 0, W = 0;
     if (grid_ratios(tot, tl, tw, map, mean, ratio)) {
@@ -801,6 +816,205 @@ extern "C" int strive_traffic_eval_metrics(const float* pred, const float* gt, c
     // latency-bound: a scene's wave-owned flags (n x NS of them) spread over up to 8 workgroups
     const int parts = NS >= 15 ? 8 : (NS >= 2 ? (NS + 1) / 2 : 1);
     hipLaunchKernelGGL(traffic_eval_kernel, dim3(B, parts), dim3(TE_NT), 0, (hipStream_t)stream, A, m);
+    STRIVE_CHECK_LAUNCH();
+    return 0;
+}
+
+// =============================================================================================
+// Collision verdicts of the refine driver (reference src/refine_traffic_optim.py:84-121, compute_metrics) for B scenes in one host
+// call without a host synchronisation, each scene as if compute_metrics had been called on that scene alone.  traj (NA,T,4) and
+// lw (NA,2) arrive NORMALISED and are unnormalised in fp32 as in strive_traffic_eval_metrics (unnorm1); everything after that is
+// float64.  Two launches:
+//   refine_grid_kernel, one workgroup per scene: the scene's status and ITS OWN sampling grid (check_on_layer, reference
+//        src/datasets/nuscenes_utils.py:266-298, forms L = round(mean_l / mean(dx)), W likewise, from the rows of one call, and the
+//        reference calls it per scene): thread t counts the valid frames of the agents t, t + 256, ... in that order and adds
+//        count * size, thread 0 adds the 256 partial sums in thread order (te_row_sums).  A scene without a valid row has no grid:
+//        L = W = 0, ratios NaN, no environment collision.  It also writes the scene's row of out_i with both counts 0 and success 1.
+//   refine_verdict_kernel, gridDim.y workgroups per scene: ONE WAVE owns a flag.
+//        did_veh[i] (check_pairwise_veh_coll, reference src/losses/adv_gen_nusc.py:567-623): agent i overlaps (IoU > 0.02) some
+//        agent j > i of its scene at some step; a frame with a NaN in either pose is no hit.  The reference's early exits make
+//        coll_count the number of set flags, and the set does not depend on the order of evaluation: the lanes stride over (j, t),
+//        reject by centre distance (boxes_apart), clip the rest (boxes_hit) and vote.
+//        did_env[a] (compute_coll_rate_env, reference src/losses/traffic_model.py:366-419): some valid frame has fp32(count) /
+//        fp32(L W) < fp32(0.95) on raster layer 0; the wave walks the frames in order, its lanes stride over the L x W samples and
+//        add their integer counts.
+//        Lane 0 writes the flag and, for a set flag, adds 1 to the scene's count and clears its success: integer atomics only, so
+//        a scene's outputs are bit-identical whatever else is in the batch and however many workgroups serve the scene.
+//   out_i (B,8): num_coll_veh, num_traj_veh (= n), env_coll, env_total (= n), success, L, W, valid rows (clamped to int32)
+//   grid_d (B,2): the two ratios before rounding
+//   status (B): 0 written; 2 offsets leave the arrays or n < 1; 3 map index out of range; 4 THIS scene's grid is outside
+//        1..lin_max along an axis.  Every output of a scene with a non-zero status is untouched.
+// =============================================================================================
+#define RV_NI 8
+
+struct RefineVerdictArgs {
+    const float* traj; const int32_t* ptr; const float* lw;
+    float sm[4], ss[4], am[2], asd[2];
+    const int32_t* mapix; const float* lin_tab; int lin_max;
+    int NA, T;
+    int32_t* did_veh; int32_t* did_env; int32_t* out_i; double* grid_d; int32_t* status;
+};
+
+__global__ __launch_bounds__(TE_NT) void refine_grid_kernel(RefineVerdictArgs A, StriveMap map) {
+#pragma clang fp contract(off)
+    __shared__ long long s_cnt[TE_NT];
+    __shared__ double s_l[TE_NT], s_w[TE_NT];
+    const int b = blockIdx.x, tid = threadIdx.x, T = A.T;
+    const int a0 = A.ptr[b], a1 = A.ptr[b + 1], n = a1 - a0;
+    int st = 0;
+    if (a0 < 0 || n <= 0 || a1 > A.NA) st = 2;
+    else if (A.mapix[b] < 0 || A.mapix[b] >= map.M) st = 3;
+    if (st != 0) {                                           // (uniform over the workgroup: nobody reaches the barrier below)
+        if (tid == 0) A.status[b] = st;
+        return;
+    }
+    long long cnt = 0;
+    double sl = 0.0, sw = 0.0;
+    for (int a = tid; a < n; a += TE_NT) {
+        const float* p = A.traj + (size_t)(a0 + a) * T * 4;
+        int c = 0;
+        for (int t = 0; t < T; ++t) {
+            float u[4];
+            te_pose(A, p + (size_t)t * 4, u);
+            c += nan4(u) ? 0 : 1;
+        }
+        if (c > 0) {
+            float lwu[2];
+            te_lw(A, a0 + a, lwu);
+            cnt += c;
+            sl += (double)c * (double)lwu[0];
+            sw += (double)c * (double)lwu[1];
+        }
+    }
+    long long tot;
+    double tl, tw;
+    te_row_sums(tid, cnt, sl, sw, s_cnt, s_l, s_w, tot, tl, tw);
+    if (tid != 0) return;
+    double mean[2], ratio[2] = {eval_nan(), eval_nan()};
+    int L = 0, W = 0;
+    if (grid_ratios(tot, tl, tw, map, mean, ratio)) {
+        const double ql = rint(ratio[0]), qw = rint(ratio[1]);
+        if (!(ql >= 1.0 && ql <= (double)A.lin_max && qw >= 1.0 && qw <= (double)A.lin_max)) {
+            A.status[b] = 4;
+            return;
+        }
+        L = (int)ql;
+        W = (int)qw;
+    }
+    int32_t* oi = A.out_i + (size_t)b * RV_NI;
+    oi[0] = 0;
+    oi[1] = n;
+    oi[2] = 0;
+    oi[3] = n;
+    oi[4] = 1;
+    oi[5] = L;
+    oi[6] = W;
+    oi[7] = tot > 0x7fffffffll ? 0x7fffffff : (int)tot;
+    A.grid_d[(size_t)b * 2 + 0] = ratio[0];
+    A.grid_d[(size_t)b * 2 + 1] = ratio[1];
+    A.status[b] = 0;
+}
+
+__global__ __launch_bounds__(TE_NT) void refine_verdict_kernel(RefineVerdictArgs A, StriveMap map) {
+#pragma clang fp contract(off)
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, T = A.T;
+    const int wave = blockIdx.y * (TE_NT / 64) + (tid >> 6), nwaves = gridDim.y * (TE_NT / 64);
+    if (A.status[b] != 0) return;                            // (refine_grid_kernel checked the offsets and the map index)
+    const int a0 = A.ptr[b], n = A.ptr[b + 1] - a0;
+    int32_t* oi = A.out_i + (size_t)b * RV_NI;
+
+    // ---- veh: one wave per agent flag ----
+    for (int i = wave; i < n; i += nwaves) {
+        const int items = (n - 1 - i) * T;
+        float lwi[2];
+        te_lw(A, a0 + i, lwi);
+        const float* pi = A.traj + (size_t)(a0 + i) * T * 4;
+        bool hit = false;
+        for (int base = 0; base < items && !hit; base += 64) {
+            const int e = base + lane;
+            bool h = false;
+            if (e < items) {
+                const int dj = e / T, t = e - dj * T, j = i + 1 + dj;
+                float u[4], v[4], lwj[2];
+                te_pose(A, pi + (size_t)t * 4, u);
+                te_pose(A, A.traj + ((size_t)(a0 + j) * T + t) * 4, v);
+                te_lw(A, a0 + j, lwj);
+                h = !boxes_apart(u, lwi, v, lwj) && boxes_hit(u, lwi, v, lwj);
+            }
+            hit = __ballot(h ? 1 : 0) != 0ull;
+        }
+        if (lane == 0) {
+            A.did_veh[a0 + i] = hit ? 1 : 0;
+            if (hit) {
+                atomicAdd(&oi[0], 1);
+                atomicExch(&oi[4], 0);
+            }
+        }
+    }
+
+    // ---- env: one wave per agent flag, frames in order, lanes over the scene's sampling grid ----
+    const int L = oi[5], W = oi[6], m = A.mapix[b], cells = L * W;
+    const float* lin_l = A.lin_tab + (size_t)L * (L > 0 ? L - 1 : 0) / 2;         // linspace(-1, 1, k) starts at k (k - 1) / 2
+    const float* lin_w = A.lin_tab + (size_t)W * (W > 0 ? W - 1 : 0) / 2;
+    const float thresh = (float)(1.0 - 0.05), area = (float)cells;
+    for (int a = wave; a < n; a += nwaves) {
+        float lwa[2];
+        te_lw(A, a0 + a, lwa);
+        bool hit = false;
+        for (int t = 0; cells > 0 && t < T && !hit; ++t) {
+            float u[4];
+            te_pose(A, A.traj + ((size_t)(a0 + a) * T + t) * 4, u);
+            if (nan4(u)) continue;
+            const CropFrame fr = map_frame(map, m, u);
+            int on = 0;
+            for (int c = lane; c < cells; c += 64) {
+                const int i = c / W, j = c - i * W;
+                on += on_road(fr, grid_coord(lin_l[i], lwa[0]), grid_coord(lin_w[j], lwa[1]));
+            }
+            for (int k = 32; k >= 1; k >>= 1) on += __shfl_xor(on, k);
+            hit = __fdiv_rn((float)on, area) < thresh;
+        }
+        if (lane == 0) {
+            A.did_env[a0 + a] = hit ? 1 : 0;
+            if (hit) {
+                atomicAdd(&oi[2], 1);
+                atomicExch(&oi[4], 0);
+            }
+        }
+    }
+}
+
+extern "C" int strive_refine_verdicts(const float* traj, const int32_t* ptr, const float* lw, const float* state_mean4_host,
+                                      const float* state_std4_host, const float* att_mean2_host, const float* att_std2_host,
+                                      const StriveMap* map, const int32_t* mapix, const float* lin_tab, int32_t lin_max, int32_t B,
+                                      int32_t NA, int32_t T, int32_t* did_veh, int32_t* did_env, int32_t* out_i, double* grid_d,
+                                      int32_t* status, strive_stream_t stream) {
+    STRIVE_CHECK_ARG(traj && ptr && lw && did_veh && did_env && out_i && grid_d && status, "null argument");
+    STRIVE_CHECK_ARG(state_mean4_host && state_std4_host && att_mean2_host && att_std2_host, "null normaliser statistics");
+    STRIVE_CHECK_ARG(map && mapix && lin_tab && lin_max >= 1, "the verdicts need a map, mapix and the linspace table");
+    STRIVE_CHECK_ARG(map->raster && map->dx && map->M >= 1 && map->C >= 1 && map->H >= 1 && map->W >= 1, "bad map");
+    STRIVE_CHECK_ARG(NA >= 0 && T >= 1 && (long long)NA * T < 0x7fffffffll, "bad sizes");
+    if (B <= 0) return 0;
+    RefineVerdictArgs A;
+    A.traj = traj; A.ptr = ptr; A.lw = lw;
+    for (int c = 0; c < 4; ++c) {
+        A.sm[c] = state_mean4_host[c];
+        A.ss[c] = state_std4_host[c];
+    }
+    for (int c = 0; c < 2; ++c) {
+        A.am[c] = att_mean2_host[c];
+        A.asd[c] = att_std2_host[c];
+    }
+    A.mapix = mapix; A.lin_tab = lin_tab; A.lin_max = lin_max;
+    A.NA = NA; A.T = T;
+    A.did_veh = did_veh; A.did_env = did_env; A.out_i = out_i; A.grid_d = grid_d; A.status = status;
+    hipLaunchKernelGGL(refine_grid_kernel, dim3(B), dim3(TE_NT), 0, (hipStream_t)stream, A, *map);
+    STRIVE_CHECK_LAUNCH();
+    // latency-bound like traffic_eval_kernel: a scene's 2 n wave-owned flags spread over up to 8 workgroups of 4 waves, by the
+    // mean scene size (the host holds no per-scene count)
+    const int flags = 2 * ((NA + B - 1) / B);
+    const int want = (flags + 3) / 4, parts = want < 1 ? 1 : (want > 8 ? 8 : want);
+    hipLaunchKernelGGL(refine_verdict_kernel, dim3(B, parts), dim3(TE_NT), 0, (hipStream_t)stream, A, *map);
     STRIVE_CHECK_LAUNCH();
     return 0;
 }

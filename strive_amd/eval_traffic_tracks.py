@@ -40,7 +40,7 @@ def tracks_loader(cfg, device):
     raster, dx = synth.make_raster(M=nmaps)
     map_env = synth.SyntheticMapEnv(raster, dx).to(device)
     ds = NuScenesDataset(tr, map_env, categories=cats, npast=cfg.get('past_len', 4), nfuture=cfg.get('future_len', 12),
-                         scenario_path=cfg.get('scenario_path'), device=device)
+                         seq_interval=cfg.get('seq_interval', 1), scenario_path=cfg.get('scenario_path'), device=device)
     return ds.loader(cfg.get('batch_size', 8)), map_env
 
 
