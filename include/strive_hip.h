@@ -565,6 +565,59 @@ int strive_refine_verdicts(const float* traj, const int32_t* ptr, const float* l
                            int32_t NA, int32_t T, int32_t* did_veh, int32_t* did_env, int32_t* out_i, double* grid_d,
                            int32_t* status, strive_stream_t stream);
 
+/* Ego-against-others verdicts of the scenario generator (check_single_veh_coll, reference src/losses/adv_gen_nusc.py:517-565, with
+ * what compute_adv_gen_success, reference src/utils/adv_gen_optim.py:214-235, and compute_sol_success, reference
+ * src/utils/sol_optim.py:126-165, read from it) for B scenes in one launch without a host synchronisation, each scene as if judged
+ * alone: float64 on the fp32 inputs, any scene size, no atomics.
+ *   traj (NA,T,4) and lw (NA,2) NORMALISED, unnormalised in fp32 with the four host arrays; ptr (B+1) agent offsets, agent 0 of a
+ *   scene is its ego; atk (B) the local attacker index 1..n-1 or -1, NULL = no attacker anywhere; want_env != 0 asks for the ego's
+ *   drivable test and needs map + mapix (B) + lin_tab / lin_max as for strive_refine_verdicts (otherwise they may be NULL).
+ *   hit (NA) int32    : the other agent overlaps the ego (IoU > 0.02) at some step; NaN frames never hit
+ *   coll_t (NA) int32 : the first such step, T if none.  The ego's own row of hit / coll_t holds the scene's n_hit > 0 / first_t.
+ *   out_i (B,8) int32 : n_others, n_hit, atk_hit (-1 without an attacker), first_t, ego_env (the ego's did_collide of
+ *         compute_coll_rate_env(ego_only=True) on that scene alone: the grid L = round(l / mean(dx)), W likewise, from the ego's
+ *         valid frames; -1 if not asked), L, W, valid ego rows
+ *   grid_d (B,2)      : the two ratios before rounding (NaN if not asked or no valid ego row)
+ *   status (B) int32  : 0 = written; 2 = offsets leave the arrays, n < 1, or an attacker index other than -1 outside 1..n-1;
+ *         3 = map index out of range; 4 = the grid is outside 1..lin_max.  Every output of a scene with a non-zero status is untouched.
+ * A scene's outputs are bit-identical whatever else is in the batch. */
+int strive_ego_verdicts(const float* traj, const int32_t* ptr, const float* lw, const int32_t* atk,
+                        const float* state_mean4_host, const float* state_std4_host, const float* att_mean2_host,
+                        const float* att_std2_host, int32_t want_env, const StriveMap* map, const int32_t* mapix,
+                        const float* lin_tab, int32_t lin_max, int32_t B, int32_t NA, int32_t T, int32_t* hit, int32_t* coll_t,
+                        int32_t* out_i, double* grid_d, int32_t* status, strive_stream_t stream);
+
+/* Feasibility screening of the scenario generator (determine_feasibility_nusc, reference src/utils/scenario_gen.py:30-107, with
+ * check_line_layer, reference src/datasets/nuscenes_utils.py:300-332, and the two ego-speed rules of reference
+ * src/adv_scenario_gen.py:176-195) for B scenes in one launch without a host synchronisation, each scene as if screened alone.
+ *   samples (NA,NS,FT,4) NORMALISED (FT >= 2), agent 0 of a scene is its ego; gt (NA,Tg,4) NORMALISED or NULL, only each scene's ego
+ *   row is read; both are unnormalised in fp32 with the two host arrays.  allowed (NA) int32 or NULL: the adv_attack_with mask.
+ *   thresh (m), t0 (the first step that counts), agent_vel / ego_vel (m per step: an agent is feasible only if its largest step
+ *   displacement is > agent_vel, the ego is too slow if its largest is < ego_vel), use_infront + infront_min in [-1,1] (a step
+ *   counts only if cos(ego heading, ego -> agent) >= infront_min; coincident positions do not count), check_sep, planner_rule (which
+ *   ego speed decides verdict 1: 0 none, 1 gt, 2 the samples).
+ * Distances, cosines, speeds and line lengths are float64 on the fp32 values.  The closest approach takes the minimum over the
+ * samples first (the first sample on a tie), then over the steps (the first step on a tie); an agent with every step masked has
+ * dist = inf, step = t0, best_samp = 0.  With check_sep the line from the agent to the ego at (best_samp, step) is sampled at
+ * sep_n points start (1 - w) + end w, w = linspace(0,1,sep_n), in fp32, divided by the map's dx in float64 and rounded half to even;
+ * sep_n = max over THAT SCENE's non-ego agents of round(|agent - ego| / mean(dx)) (mean over all entries of the map pack's dx).
+ *   per non-ego agent (the ego's rows are untouched): feasible (within, no line sample on a 0 pixel, fast enough, allowed), within,
+ *         step, best_samp, sep_zero (line samples on a 0 pixel) int32; dist, max_vel double
+ *   out_i (B,8) int32 : n_others, n_within, n_feasible_any_category, n_feasible, heur_agt (local index of the feasible agent with the
+ *         smallest dist, the lowest index on a tie, -1 if none), heur_t (its step, -1), sep_n, verdict: 1 = ego too slow, 2 = ego
+ *         only, 3 = no vehicle near, 4 = no feasible attacker of the requested category, 0 = feasible (the reference's order)
+ *   out_d (B,3)       : the ego's largest step displacement over the samples, over gt (NaN without gt or Tg < 2), heur_dist (inf if none)
+ *   status (B) int32  : 0 = written; 2 = offsets leave the arrays or n < 1; 3 = map index out of range; 5 = a sample is not finite;
+ *         6 = a line sample lies outside the raster (torch would raise or wrap) or sep_n > 65536.  Every output of a scene with a
+ *         non-zero status is untouched.
+ * No atomics; a scene's outputs are bit-identical whatever else is in the batch. */
+int strive_feasibility_screen(const float* samples, const int32_t* ptr, const int32_t* mapix, const int32_t* allowed, const float* gt,
+                              const float* state_mean4_host, const float* state_std4_host, const StriveMap* map, double thresh,
+                              int32_t t0, double agent_vel, double ego_vel, int32_t use_infront, double infront_min,
+                              int32_t check_sep, int32_t planner_rule, int32_t B, int32_t NA, int32_t NS, int32_t FT, int32_t Tg,
+                              int32_t* feasible, int32_t* within, int32_t* step, int32_t* best_samp, double* dist, int32_t* sep_zero,
+                              double* max_vel, int32_t* out_i, double* out_d, int32_t* status, strive_stream_t stream);
+
 /* One Lloyd step of k-means on x (N,F) float64 with centers (k,F), F = 1..8, k = 1..64 (the clustering of reference
  * src/cluster_scenarios.py, which calls scikit-learn's KMeans on the host): labels (N) = nearest centre, the lowest index on
  * equal squared distance; mind (N) that distance; sums (k,F) and counts (k) per cluster; inertia (1) = sum of mind.  Two

@@ -185,6 +185,9 @@ PROTOTYPES = {
     'strive_traffic_eval_metrics': (C.c_int, [P, P, P, P, P, F4, F4, F4, F4, C.POINTER(StriveMap), P, P, I, I, I, I, I, I, I, I,
                                                P, P, P, P, P, P, P, P, P]),
     'strive_refine_verdicts': (C.c_int, [P, P, P, F4, F4, F4, F4, C.POINTER(StriveMap), P, P, I, I, I, I, P, P, P, P, P, P]),
+    'strive_ego_verdicts': (C.c_int, [P, P, P, P, F4, F4, F4, F4, I, C.POINTER(StriveMap), P, P, I, I, I, I, P, P, P, P, P, P]),
+    'strive_feasibility_screen': (C.c_int, [P, P, P, P, P, F4, F4, C.POINTER(StriveMap), C.c_double, I, C.c_double, C.c_double, I,
+                                            C.c_double, I, I, I, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P]),
     'strive_kmeans_step': (C.c_int, [P, P, I, I, I, P, P, P, P, P, P]),
     'strive_veh_coll_bwd': (C.c_int, [C.POINTER(StriveScenes), P, I, P, I, P, P, C.c_float, P, P, P, P]),
     'strive_avoid_coll_workspace_bytes': (SZ, [C.POINTER(StriveScenes), C.POINTER(StriveAvoidColl), I]),

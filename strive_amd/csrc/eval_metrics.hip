@@ -1020,6 +1020,517 @@ extern "C" int strive_refine_verdicts(const float* traj, const int32_t* ptr, con
 }
 
 // =============================================================================================
+// Ego-against-others verdicts of the scenario generator (check_single_veh_coll, reference src/losses/adv_gen_nusc.py:517-565, as
+// compute_adv_gen_success, reference src/utils/adv_gen_optim.py:214-235, and compute_sol_success, reference
+// src/utils/sol_optim.py:126-165, call it) for B scenes in one launch without a host synchronisation, each scene as if judged
+// alone.  traj (NA,T,4) and lw (NA,2) arrive NORMALISED and are unnormalised in fp32 (unnorm1); everything after that is float64.
+// One workgroup of EV_NW waves per scene:
+//   thread 0 forms the scene's status and, if asked, the sampling grid of ITS ego rows alone (compute_coll_rate_env with
+//        ego_only=True on a single scene hands check_on_layer the ego's valid frames and nothing else);
+//   wave w owns the other agents 1 + w, 1 + w + EV_NW, ...: its lanes take the steps in order, 64 at a time, reject by centre distance
+//        (boxes_apart), clip the rest (boxes_hit) and vote; the lowest set lane of the first non-empty vote is the collision step;
+//   wave w owns the ego frames w, w + EV_NW, ... of the drivable test, its lanes stride over the L x W samples (integer counts);
+//   thread 0 adds the waves' integer counts in wave order.  No atomics at all.
+//   hit (NA), coll_t (NA): per other agent; the ego's row holds the scene's own n_hit > 0 and first_t
+//   out_i (B,8): n_others, n_hit, atk_hit (-1 without an attacker), first_t (T if none), ego_env (-1 if not asked), L, W, valid ego rows
+//   grid_d (B,2): the two ratios before rounding (NaN if not asked or without a valid ego row)
+//   status (B): 0 written; 2 offsets leave the arrays, n < 1 or an attacker index other than -1 outside 1..n-1; 3 map index out of
+//        range; 4 the scene's grid is outside 1..lin_max.  Every output of a scene with a non-zero status is untouched.
+// =============================================================================================
+#define EV_NI 8
+#define EV_NW (TE_NT / 64)
+
+struct EgoVerdictArgs {
+    const float* traj; const int32_t* ptr; const float* lw; const int32_t* atk;
+    float sm[4], ss[4], am[2], asd[2];
+    const int32_t* mapix; const float* lin_tab; int lin_max, want_env;
+    int NA, T;
+    int32_t* hit; int32_t* coll_t; int32_t* out_i; double* grid_d; int32_t* status;
+};
+
+__global__ __launch_bounds__(TE_NT) void ego_verdict_kernel(EgoVerdictArgs A, StriveMap map) {
+#pragma clang fp contract(off)
+    __shared__ int s_grid[4], s_atk, s_hit[EV_NW], s_first[EV_NW], s_env[EV_NW];
+    __shared__ double s_ratio[2];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, T = A.T;
+    const int a0 = A.ptr[b], a1 = A.ptr[b + 1], n = a1 - a0;
+    const int atk = A.atk ? A.atk[b] : -1;
+    int st = 0;
+    if (a0 < 0 || n <= 0 || a1 > A.NA || (atk != -1 && (atk < 1 || atk >= n))) st = 2;
+    else if (A.want_env && (A.mapix[b] < 0 || A.mapix[b] >= map.M)) st = 3;
+    if (st != 0) {                                           // (uniform over the workgroup: nobody reaches the barriers below)
+        if (tid == 0) A.status[b] = st;
+        return;
+    }
+    float lwe[2];
+    te_lw(A, a0, lwe);
+    const float* pe = A.traj + (size_t)a0 * T * 4;
+    if (tid == 0) {
+        int L = 0, W = 0, rows = 0, bad = 0;
+        double mean[2], ratio[2] = {eval_nan(), eval_nan()};
+        if (A.want_env) {
+            for (int t = 0; t < T; ++t) {
+                float u[4];
+                te_pose(A, pe + (size_t)t * 4, u);
+                rows += nan4(u) ? 0 : 1;
+            }
+            if (grid_ratios(rows, (double)rows * (double)lwe[0], (double)rows * (double)lwe[1], map, mean, ratio)) {
+                const double ql = rint(ratio[0]), qw = rint(ratio[1]);
+                if (ql >= 1.0 && ql <= (double)A.lin_max && qw >= 1.0 && qw <= (double)A.lin_max) {
+                    L = (int)ql;
+                    W = (int)qw;
+                } else {
+                    bad = 1;
+                }
+            }
+        }
+        s_grid[0] = bad; s_grid[1] = L; s_grid[2] = W; s_grid[3] = rows;
+        s_ratio[0] = ratio[0]; s_ratio[1] = ratio[1];
+        s_atk = -1;
+    }
+    __syncthreads();
+    if (s_grid[0] != 0) {
+        if (tid == 0) A.status[b] = 4;
+        return;
+    }
+
+    // ---- the ego against each other agent: one wave per agent, the steps in order ----
+    int cnt = 0, first = T;
+    for (int j = 1 + wave; j < n; j += EV_NW) {
+        float lwj[2];
+        te_lw(A, a0 + j, lwj);
+        const float* pj = A.traj + (size_t)(a0 + j) * T * 4;
+        int ct = T;
+        for (int base = 0; base < T && ct == T; base += 64) {
+            const int t = base + lane;
+            bool h = false;
+            if (t < T) {
+                float u[4], v[4];
+                te_pose(A, pe + (size_t)t * 4, u);
+                te_pose(A, pj + (size_t)t * 4, v);
+                h = !boxes_apart(u, lwe, v, lwj) && boxes_hit(u, lwe, v, lwj);
+            }
+            const unsigned long long m = __ballot(h ? 1 : 0);
+            if (m != 0ull) ct = base + __ffsll((long long)m) - 1;
+        }
+        cnt += ct < T ? 1 : 0;
+        first = ct < first ? ct : first;
+        if (lane == 0) {
+            A.hit[a0 + j] = ct < T ? 1 : 0;
+            A.coll_t[a0 + j] = ct;
+            if (j == atk) s_atk = ct < T ? 1 : 0;
+        }
+    }
+
+    // ---- the ego on the drivable area: one wave per frame, lanes over the scene's sampling grid ----
+    const int L = s_grid[1], W = s_grid[2], cells = L * W;
+    int env = 0;
+    if (A.want_env && cells > 0) {
+        const int m = A.mapix[b];
+        const float* lin_l = A.lin_tab + (size_t)L * (L - 1) / 2;                 // linspace(-1, 1, k) starts at k (k - 1) / 2
+        const float* lin_w = A.lin_tab + (size_t)W * (W - 1) / 2;
+        const float thresh = (float)(1.0 - 0.05), area = (float)cells;
+        for (int t = wave; t < T && !env; t += EV_NW) {
+            float u[4];
+            te_pose(A, pe + (size_t)t * 4, u);
+            if (nan4(u)) continue;
+            const CropFrame fr = map_frame(map, m, u);
+            int on = 0;
+            for (int c = lane; c < cells; c += 64) {
+                const int i = c / W, k = c - i * W;
+                on += on_road(fr, grid_coord(lin_l[i], lwe[0]), grid_coord(lin_w[k], lwe[1]));
+            }
+            for (int k = 32; k >= 1; k >>= 1) on += __shfl_xor(on, k);
+            env = __fdiv_rn((float)on, area) < thresh ? 1 : 0;
+        }
+    }
+    if (lane == 0) {
+        s_hit[wave] = cnt;
+        s_first[wave] = first;
+        s_env[wave] = env;
+    }
+    __syncthreads();
+    if (tid != 0) return;
+    int n_hit = 0, first_t = T, ego_env = 0;
+    for (int w = 0; w < EV_NW; ++w) {
+        n_hit += s_hit[w];
+        first_t = s_first[w] < first_t ? s_first[w] : first_t;
+        ego_env |= s_env[w];
+    }
+    int32_t* oi = A.out_i + (size_t)b * EV_NI;
+    oi[0] = n - 1;
+    oi[1] = n_hit;
+    oi[2] = atk == -1 ? -1 : s_atk;
+    oi[3] = first_t;
+    oi[4] = A.want_env ? ego_env : -1;
+    oi[5] = L;
+    oi[6] = W;
+    oi[7] = s_grid[3];
+    A.grid_d[(size_t)b * 2 + 0] = s_ratio[0];
+    A.grid_d[(size_t)b * 2 + 1] = s_ratio[1];
+    A.hit[a0] = n_hit > 0 ? 1 : 0;
+    A.coll_t[a0] = first_t;
+    A.status[b] = 0;
+}
+
+extern "C" int strive_ego_verdicts(const float* traj, const int32_t* ptr, const float* lw, const int32_t* atk,
+                                   const float* state_mean4_host, const float* state_std4_host, const float* att_mean2_host,
+                                   const float* att_std2_host, int32_t want_env, const StriveMap* map, const int32_t* mapix,
+                                   const float* lin_tab, int32_t lin_max, int32_t B, int32_t NA, int32_t T, int32_t* hit,
+                                   int32_t* coll_t, int32_t* out_i, double* grid_d, int32_t* status, strive_stream_t stream) {
+    STRIVE_CHECK_ARG(traj && ptr && lw && hit && coll_t && out_i && grid_d && status, "null argument");
+    STRIVE_CHECK_ARG(state_mean4_host && state_std4_host && att_mean2_host && att_std2_host, "null normaliser statistics");
+    STRIVE_CHECK_ARG(!want_env || (map && mapix && lin_tab && lin_max >= 1), "want_env needs a map, mapix and the linspace table");
+    STRIVE_CHECK_ARG(!want_env || (map->raster && map->dx && map->M >= 1 && map->C >= 1 && map->H >= 1 && map->W >= 1), "bad map");
+    STRIVE_CHECK_ARG(NA >= 0 && T >= 1 && (long long)NA * T < 0x7fffffffll, "bad sizes");
+    if (B <= 0) return 0;
+    EgoVerdictArgs A;
+    A.traj = traj; A.ptr = ptr; A.lw = lw; A.atk = atk;
+    for (int c = 0; c < 4; ++c) {
+        A.sm[c] = state_mean4_host[c];
+        A.ss[c] = state_std4_host[c];
+    }
+    for (int c = 0; c < 2; ++c) {
+        A.am[c] = att_mean2_host[c];
+        A.asd[c] = att_std2_host[c];
+    }
+    A.mapix = mapix; A.lin_tab = lin_tab; A.lin_max = lin_max; A.want_env = want_env ? 1 : 0;
+    A.NA = NA; A.T = T;
+    A.hit = hit; A.coll_t = coll_t; A.out_i = out_i; A.grid_d = grid_d; A.status = status;
+    StriveMap none = {};
+    hipLaunchKernelGGL(ego_verdict_kernel, dim3(B), dim3(TE_NT), 0, (hipStream_t)stream, A, want_env ? *map : none);
+    STRIVE_CHECK_LAUNCH();
+    return 0;
+}
+
+// =============================================================================================
+// Feasibility screening of the scenario generator (determine_feasibility_nusc, reference src/utils/scenario_gen.py:30-107, with
+// check_line_layer, reference src/datasets/nuscenes_utils.py:300-332, and the two ego-speed rules of reference
+// src/adv_scenario_gen.py:176-195) for B scenes in one launch without a host synchronisation, each scene as if screened alone.
+// samples (NA,NS,FT,4) and gt (NA,Tg,4) arrive NORMALISED and are unnormalised in fp32 (unnorm1); distances, cosines, speeds and
+// line lengths are float64 on those fp32 values; the line samples are fp32, operation for operation (fs_line_weight).
+// One workgroup of FS_NW waves per scene, a wave per non-ego agent (fs_agent: lanes over the steps, the samples of a step in order,
+// then a lexicographic (distance, step) butterfly, so the first sample and the first step win a tie).  The kernel keeps nothing per
+// agent between its phases: it walks the agents up to three times and forms the same values each time.
+//   pass 0: the scene's own line length sep_n = max over ITS agents of rint(|agent - ego| / mean(dx)) (check_line_layer takes the
+//           maximum over the rows of one call, and the reference calls it per scene)
+//   pass 1: (check_sep only) does any line sample leave the raster -> status 6, nothing written
+//   pass 2: the lines again, the outputs per agent, and the scene's counts, which thread 0 adds in wave order
+// No atomics at all, every reduction in a fixed order or order-free (integer sums, lexicographic minima, maxima without NaN).
+//   per non-ego agent (the ego's rows are untouched): feasible, within, step, best_samp, sep_zero int32; dist, max_vel double
+//   out_i (B,8): n_others, n_within, n_feasible_any_category, n_feasible, heur_agt (local index, -1 if none), heur_t (-1 if none),
+//        sep_n, verdict (1 ego too slow, 2 ego only, 3 no vehicle near, 4 none of the requested category, 0 feasible)
+//   out_d (B,3): largest ego step displacement over the samples, the same over gt's ego row (NaN without gt or with Tg < 2; a NaN
+//        in gt gives NaN), heur_dist (inf if none)
+//   status (B): 0 written; 2 offsets leave the arrays or n < 1; 3 map index out of range; 5 a sample that is not finite after
+//        unnormalising; 6 a line sample outside the raster, or sep_n above FS_LINE_MAX.  Nothing of such a scene is written.
+// =============================================================================================
+#define FS_NI 8
+#define FS_ND 3
+#define FS_NW (TE_NT / 64)
+#define FS_LINE_MAX 65536
+#define FS_NO_STEP 0x7fffffff
+
+struct FeasScreenArgs {
+    const float* samples; const int32_t* ptr; const int32_t* mapix; const int32_t* allowed; const float* gt;
+    float sm[4], ss[4];
+    double thresh, agent_vel, ego_vel, infront_min;
+    int t0, use_infront, check_sep, planner_rule;
+    int NA, NS, FT, Tg;
+    int32_t* feasible; int32_t* within; int32_t* step; int32_t* best_samp; int32_t* sep_zero;
+    double* dist; double* max_vel; int32_t* out_i; double* out_d; int32_t* status;
+};
+
+struct FsBest {
+    double dist, vel;        // closest approach after the in-front mask (inf if every step is masked); largest step displacement
+    int step, samp, within;  // where it is attained (t0, 0 if every step is masked); some distance < thresh
+};
+
+__device__ __forceinline__ double fs_inf() { return __longlong_as_double(0x7ff0000000000000ll); }
+
+// unnormalised position (and, for the ego, heading) of sample s, step t of the agent whose samples start at p
+__device__ __forceinline__ void fs_xy(const FeasScreenArgs& A, const float* p, int s, int t, float& x, float& y) {
+    const float* q = p + ((size_t)s * A.FT + t) * 4;
+    x = unnorm1(q[0], A.sm[0], A.ss[0]);
+    y = unnorm1(q[1], A.sm[1], A.ss[1]);
+}
+
+// |a - b| of two fp32 points in float64
+__device__ __forceinline__ double fs_len(float ax, float ay, float bx, float by) {
+#pragma clang fp contract(off)
+    const double dx = (double)ax - (double)bx, dy = (double)ay - (double)by;
+    return sqrt(dx * dx + dy * dy);
+}
+
+// One non-ego agent by one wave; every lane returns the same values.
+__device__ __forceinline__ FsBest fs_agent(const FeasScreenArgs& A, const float* ego, const float* agt, int lane) {
+#pragma clang fp contract(off)
+    const int NS = A.NS, FT = A.FT;
+    double bd = fs_inf();
+    int bt = FS_NO_STEP, bs = 0, within = 0;
+    for (int t = A.t0 + lane; t < FT; t += 64) {
+        double sd = fs_inf();
+        int ssamp = 0;
+        for (int s = 0; s < NS; ++s) {
+            float ex, ey, ax, ay;
+            fs_xy(A, ego, s, t, ex, ey);
+            fs_xy(A, agt, s, t, ax, ay);
+            double d = fs_len(ax, ay, ex, ey);
+            if (A.use_infront) {
+                const float* q = ego + ((size_t)s * FT + t) * 4;
+                const double hx = (double)unnorm1(q[2], A.sm[2], A.ss[2]), hy = (double)unnorm1(q[3], A.sm[3], A.ss[3]);
+                const double ux = ((double)ax - (double)ex) / d, uy = ((double)ay - (double)ey) / d;
+                const double cossim = ux * hx + uy * hy;
+                if (!(cossim >= A.infront_min)) d = fs_inf();            // (coincident positions: 0 / 0, not in front)
+            }
+            within |= d < A.thresh ? 1 : 0;
+            if (d < sd) { sd = d; ssamp = s; }
+        }
+        if (sd < bd) { bd = sd; bt = t; bs = ssamp; }
+    }
+    double vel = 0.0;
+    const int items = NS * (FT - 1);
+    for (int e = lane; e < items; e += 64) {
+        const int s = e / (FT - 1), t = e - s * (FT - 1);
+        float x0, y0, x1, y1;
+        fs_xy(A, agt, s, t, x0, y0);
+        fs_xy(A, agt, s, t + 1, x1, y1);
+        const double v = fs_len(x1, y1, x0, y0);
+        vel = v > vel ? v : vel;
+    }
+    for (int k = 32; k >= 1; k >>= 1) {
+        const double od = __shfl_xor(bd, k), ov = __shfl_xor(vel, k);
+        const int ot = __shfl_xor(bt, k), os = __shfl_xor(bs, k);
+        if (od < bd || (od == bd && ot < bt)) { bd = od; bt = ot; bs = os; }
+        vel = ov > vel ? ov : vel;
+    }
+    FsBest r;
+    r.dist = bd;
+    r.vel = vel;
+    r.step = bt == FS_NO_STEP ? A.t0 : bt;
+    r.samp = bt == FS_NO_STEP ? 0 : bs;
+    r.within = __ballot(within) != 0ull ? 1 : 0;
+    return r;
+}
+
+// torch.linspace(0, 1, n)[i] in fp32 (n >= 1): step = 1 / (n - 1); the first half counts up from 0, the second down from 1
+__device__ __forceinline__ float fs_line_weight(int i, int n) {
+    if (n < 2) return 0.0f;
+    const float step = __fdiv_rn(1.0f, (float)(n - 1));
+    return i < n / 2 ? __fmul_rn(step, (float)i) : __fsub_rn(1.0f, __fmul_rn(step, (float)(n - 1 - i)));
+}
+
+// The n samples start * (1 - w) + end * w of one line by one wave: how many lie on a 0 pixel of the frame's layer 0, and whether
+// any lies outside the raster (such a sample is not read).  Every lane returns the same values.
+__device__ __forceinline__ void fs_line(const CropFrame& fr, float sx, float sy, float ex, float ey, int n, int lane, int& zero, int& outside) {
+    int z = 0, o = 0;
+    for (int i = lane; i < n; i += 64) {
+        const float w = fs_line_weight(i, n), w1 = __fsub_rn(1.0f, w);
+        const float gx = __fadd_rn(__fmul_rn(sx, w1), __fmul_rn(ex, w));
+        const float gy = __fadd_rn(__fmul_rn(sy, w1), __fmul_rn(ey, w));
+        const double qx = quotient_rint((double)gx, fr.dx0, fr.inv0), qy = quotient_rint((double)gy, fr.dx1, fr.inv1);
+        if (qx >= 0.0 && qx < (double)fr.W && qy >= 0.0 && qy < (double)fr.H) z += fr.base[(size_t)(int)qy * fr.W + (int)qx] == 0 ? 1 : 0;
+        else o = 1;
+    }
+    for (int k = 32; k >= 1; k >>= 1) z += __shfl_xor(z, k);
+    zero = z;
+    outside = __ballot(o) != 0ull ? 1 : 0;
+}
+
+__global__ __launch_bounds__(TE_NT) void feasibility_screen_kernel(FeasScreenArgs A, StriveMap map) {
+#pragma clang fp contract(off)
+    __shared__ int s_bad[FS_NW], s_n[FS_NW], s_out[FS_NW], s_cnt[FS_NW][3], s_ha[FS_NW], s_ht[FS_NW];
+    __shared__ double s_ev[FS_NW], s_hd[FS_NW];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, NS = A.NS, FT = A.FT;
+    const int a0 = A.ptr[b], a1 = A.ptr[b + 1], n = a1 - a0;
+    int st = 0;
+    if (a0 < 0 || n <= 0 || a1 > A.NA) st = 2;
+    else if (A.mapix[b] < 0 || A.mapix[b] >= map.M) st = 3;
+    if (st != 0) {                                           // (uniform over the workgroup: nobody reaches the barriers below)
+        if (tid == 0) A.status[b] = st;
+        return;
+    }
+    const float* ego = A.samples + (size_t)a0 * NS * FT * 4;
+
+    // ---- every sample of the scene is finite; the ego's largest step displacement over its samples ----
+    int bad = 0;
+    const size_t vals = (size_t)n * NS * FT * 4;
+    for (size_t i = tid; i < vals; i += TE_NT) {
+        const int c = (int)(i & 3);
+        bad |= fabsf(unnorm1(ego[i], A.sm[c], A.ss[c])) <= 3.4028234663852886e38f ? 0 : 1;
+    }
+    double ev = 0.0;
+    for (int e = tid; e < NS * (FT - 1); e += TE_NT) {
+        const int s = e / (FT - 1), t = e - s * (FT - 1);
+        float x0, y0, x1, y1;
+        fs_xy(A, ego, s, t, x0, y0);
+        fs_xy(A, ego, s, t + 1, x1, y1);
+        const double v = fs_len(x1, y1, x0, y0);
+        ev = v > ev ? v : ev;
+    }
+    for (int k = 32; k >= 1; k >>= 1) {
+        const double ov = __shfl_xor(ev, k);
+        ev = ov > ev ? ov : ev;
+    }
+    bad = __ballot(bad) != 0ull ? 1 : 0;
+    if (lane == 0) {
+        s_bad[wave] = bad;
+        s_ev[wave] = ev;
+    }
+    __syncthreads();
+    bad = 0;
+    ev = 0.0;
+    for (int w = 0; w < FS_NW; ++w) {
+        bad |= s_bad[w];
+        ev = s_ev[w] > ev ? s_ev[w] : ev;
+    }
+    if (bad) {
+        if (tid == 0) A.status[b] = 5;
+        return;
+    }
+
+    double sdx = 0.0;
+    for (int m = 0; m < map.M * 2; ++m) sdx += map.dx[m];
+    const double mdx = sdx / (double)(map.M * 2);
+    float zero4[4] = {0.0f, 0.0f, 1.0f, 0.0f};
+    const CropFrame fr = map_frame(map, A.mapix[b], zero4);
+
+    int sep_n = 0;
+    int n_within = 0, n_any = 0, n_feas = 0, ha = -1, ht = -1;
+    double hd = fs_inf();
+    for (int pass = 0; pass < 3; ++pass) {
+        if (pass == 1 && !A.check_sep) continue;
+        int wn = 0, wout = 0;
+        for (int j = 1 + wave; j < n; j += FS_NW) {
+            const float* agt = A.samples + (size_t)(a0 + j) * NS * FT * 4;
+            const FsBest r = fs_agent(A, ego, agt, lane);
+            float ax, ay, ex, ey;
+            fs_xy(A, agt, r.samp, r.step, ax, ay);
+            fs_xy(A, ego, r.samp, r.step, ex, ey);
+            if (pass == 0) {
+                const double q = rint(fs_len(ax, ay, ex, ey) / mdx);
+                const int na = q <= (double)FS_LINE_MAX ? (int)q : FS_LINE_MAX + 1;
+                wn = na > wn ? na : wn;
+                continue;
+            }
+            int zero = 0, outside = 0;
+            if (A.check_sep) fs_line(fr, ax, ay, ex, ey, sep_n, lane, zero, outside);
+            wout |= outside;
+            if (pass == 1) continue;
+            const int any = (r.within && zero == 0 && r.vel > A.agent_vel) ? 1 : 0;
+            const int feas = (any && (!A.allowed || A.allowed[a0 + j] != 0)) ? 1 : 0;
+            n_within += r.within;
+            n_any += any;
+            n_feas += feas;
+            if (feas && (r.dist < hd || (r.dist == hd && j < ha))) { hd = r.dist; ha = j; ht = r.step; }
+            if (lane == 0) {
+                A.feasible[a0 + j] = feas;
+                A.within[a0 + j] = r.within;
+                A.step[a0 + j] = r.step;
+                A.best_samp[a0 + j] = r.samp;
+                A.sep_zero[a0 + j] = zero;
+                A.dist[a0 + j] = r.dist;
+                A.max_vel[a0 + j] = r.vel;
+            }
+        }
+        if (pass == 0) {
+            if (lane == 0) s_n[wave] = wn;
+            __syncthreads();
+            for (int w = 0; w < FS_NW; ++w) sep_n = s_n[w] > sep_n ? s_n[w] : sep_n;
+            if (sep_n > FS_LINE_MAX) {
+                if (tid == 0) A.status[b] = 6;
+                return;
+            }
+        } else if (pass == 1) {
+            if (lane == 0) s_out[wave] = wout;
+            __syncthreads();
+            wout = 0;
+            for (int w = 0; w < FS_NW; ++w) wout |= s_out[w];
+            if (wout) {
+                if (tid == 0) A.status[b] = 6;
+                return;
+            }
+        }
+    }
+    if (lane == 0) {
+        s_cnt[wave][0] = n_within; s_cnt[wave][1] = n_any; s_cnt[wave][2] = n_feas;
+        s_ha[wave] = ha; s_ht[wave] = ht; s_hd[wave] = hd;
+    }
+    __syncthreads();
+    if (tid != 0) return;
+    n_within = n_any = n_feas = 0;
+    ha = ht = -1;
+    hd = fs_inf();
+    for (int w = 0; w < FS_NW; ++w) {
+        n_within += s_cnt[w][0];
+        n_any += s_cnt[w][1];
+        n_feas += s_cnt[w][2];
+        if (s_ha[w] >= 0 && (s_hd[w] < hd || (s_hd[w] == hd && s_ha[w] < ha))) { hd = s_hd[w]; ha = s_ha[w]; ht = s_ht[w]; }
+    }
+    // the ego's largest step displacement over gt's ego row, as torch.max gives it: a NaN wins
+    double gv = eval_nan();
+    if (A.gt && A.Tg >= 2) {
+        const float* g = A.gt + (size_t)a0 * A.Tg * 4;
+        gv = 0.0;
+        for (int t = 0; t + 1 < A.Tg; ++t) {
+            const float x0 = unnorm1(g[t * 4 + 0], A.sm[0], A.ss[0]), y0 = unnorm1(g[t * 4 + 1], A.sm[1], A.ss[1]);
+            const float x1 = unnorm1(g[t * 4 + 4], A.sm[0], A.ss[0]), y1 = unnorm1(g[t * 4 + 5], A.sm[1], A.ss[1]);
+            const double v = fs_len(x1, y1, x0, y0);
+            gv = (gv != gv || v != v) ? (gv + v) : (v > gv ? v : gv);
+        }
+    }
+    const double ego_v = A.planner_rule == 1 ? gv : ev;
+    const bool slow = A.planner_rule != 0 && ego_v < A.ego_vel;
+    int32_t* oi = A.out_i + (size_t)b * FS_NI;
+    oi[0] = n - 1;
+    oi[1] = n_within;
+    oi[2] = n_any;
+    oi[3] = n_feas;
+    oi[4] = ha;
+    oi[5] = ht;
+    oi[6] = sep_n;
+    oi[7] = slow ? 1 : (n == 1 ? 2 : (n_any == 0 ? 3 : (n_feas == 0 ? 4 : 0)));
+    double* od = A.out_d + (size_t)b * FS_ND;
+    od[0] = ev;
+    od[1] = gv;
+    od[2] = hd;
+    A.status[b] = 0;
+}
+
+extern "C" int strive_feasibility_screen(const float* samples, const int32_t* ptr, const int32_t* mapix, const int32_t* allowed,
+                                         const float* gt, const float* state_mean4_host, const float* state_std4_host,
+                                         const StriveMap* map, double thresh, int32_t t0, double agent_vel, double ego_vel,
+                                         int32_t use_infront, double infront_min, int32_t check_sep, int32_t planner_rule, int32_t B,
+                                         int32_t NA, int32_t NS, int32_t FT, int32_t Tg, int32_t* feasible, int32_t* within,
+                                         int32_t* step, int32_t* best_samp, double* dist, int32_t* sep_zero, double* max_vel,
+                                         int32_t* out_i, double* out_d, int32_t* status, strive_stream_t stream) {
+    STRIVE_CHECK_ARG(samples && ptr && mapix && feasible && within && step && best_samp && dist && sep_zero && max_vel, "null argument");
+    STRIVE_CHECK_ARG(out_i && out_d && status && state_mean4_host && state_std4_host, "null argument");
+    STRIVE_CHECK_ARG(map && map->raster && map->dx && map->M >= 1 && map->C >= 1 && map->H >= 1 && map->W >= 1, "bad map");
+    STRIVE_CHECK_ARG(NA >= 0 && NS >= 1 && FT >= 2 && (long long)NA * NS * FT < 0x1fffffffll, "bad sizes");
+    STRIVE_CHECK_ARG(t0 >= 0 && t0 < FT, "feasibility_time outside the horizon");
+    STRIVE_CHECK_ARG(!use_infront || (infront_min >= -1.0 && infront_min <= 1.0), "feasibility_infront_min must lie in [-1, 1]");
+    STRIVE_CHECK_ARG(planner_rule >= 0 && planner_rule <= 2, "planner_rule is 0 (none), 1 (gt) or 2 (samples)");
+    STRIVE_CHECK_ARG(planner_rule != 1 || (gt && Tg >= 2), "the gt rule needs gt with at least two steps");
+    STRIVE_CHECK_ARG(!gt || (Tg >= 1 && (long long)NA * Tg < 0x1fffffffll), "bad gt size");
+    if (B <= 0) return 0;
+    FeasScreenArgs A;
+    A.samples = samples; A.ptr = ptr; A.mapix = mapix; A.allowed = allowed; A.gt = gt;
+    for (int c = 0; c < 4; ++c) {
+        A.sm[c] = state_mean4_host[c];
+        A.ss[c] = state_std4_host[c];
+    }
+    A.thresh = thresh; A.agent_vel = agent_vel; A.ego_vel = ego_vel; A.infront_min = infront_min;
+    A.t0 = t0; A.use_infront = use_infront ? 1 : 0; A.check_sep = check_sep ? 1 : 0; A.planner_rule = planner_rule;
+    A.NA = NA; A.NS = NS; A.FT = FT; A.Tg = Tg;
+    A.feasible = feasible; A.within = within; A.step = step; A.best_samp = best_samp; A.sep_zero = sep_zero;
+    A.dist = dist; A.max_vel = max_vel; A.out_i = out_i; A.out_d = out_d; A.status = status;
+    hipLaunchKernelGGL(feasibility_screen_kernel, dim3(B), dim3(TE_NT), 0, (hipStream_t)stream, A, *map);
+    STRIVE_CHECK_LAUNCH();
+    return 0;
+}
+
+// =============================================================================================
 // One Lloyd step of k-means on N x F float64 features (the clustering of reference src/cluster_scenarios.py, whose
 // KMeans.fit / .predict run scikit-learn on the host): every row's nearest centre (squared distance summed over the
 // features in order, the lowest index on equal distance), then per-cluster sums and counts and the inertia.  No atomics on

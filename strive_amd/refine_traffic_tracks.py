@@ -372,35 +372,39 @@ ARGUMENTS = (
 )
 
 
-def get_parser():
+def get_parser(arguments=ARGUMENTS, description='Sample+optim motion model on a tracks file', optimiser_switch=True):
+    """The command line of a driver from its ARGUMENTS table (``optimiser_switch``: this driver's ``--optim_use_lbfgs``)."""
     import argparse
-    p = argparse.ArgumentParser(description='Sample+optim motion model on a tracks file')
+    p = argparse.ArgumentParser(description=description)
     p.add_argument('-c', '--config', type=str, default=None, help='file of `key: value` lines; the command line wins over it')
-    for name, kind, default, text in ARGUMENTS:
+    for name, kind, default, text in arguments:
         if kind is bool:
             p.add_argument('--' + name, action='store_true', default=default, help=text)
         elif isinstance(kind, list):
             p.add_argument('--' + name, type=kind[0], nargs='+', default=default, help=text)
         else:
             p.add_argument('--' + name, type=kind, default=default, help=text)
-    p.add_argument('--optim_use_lbfgs', dest='optim_use_adam', action='store_false', default=True,
-                   help='LBFGS (20 inner iterations, strong-Wolfe line search) instead of Adam')
+    if optimiser_switch:
+        p.add_argument('--optim_use_lbfgs', dest='optim_use_adam', action='store_false', default=True,
+                       help='LBFGS (20 inner iterations, strong-Wolfe line search) instead of Adam')
     return p
 
 
-def parse_cfg(argv=None):
+def parse_cfg(argv=None, arguments=ARGUMENTS, parser=None, ignored_keys=IGNORED_KEYS):
     """Defaults < ``--config`` file < command line, by the rules of ``train_traffic.parse_cfg``: an unknown key in the file is an
     error; the keys that describe the devkit's data or ask for rendering (IGNORED_KEYS) are accepted and ignored, and reported.  A
-    flag is ``key: True`` / ``key: False`` in the file.  Returns the config dict and the ignored keys."""
-    p = get_parser()
+    flag is ``key: True`` / ``key: False`` in the file.  Returns the config dict and the ignored keys.  (``arguments``, ``parser``,
+    ``ignored_keys``: another driver's table, the parser made from it and its ignored keys.)"""
+    p = get_parser() if parser is None else parser
     argv = list(__import__('sys').argv[1:] if argv is None else argv)
     pre, _ = p.parse_known_args(argv)
     ignored, file_args = [], []
     if pre.config is not None:
         known = {a.dest: a for a in p._actions}
-        flags = {name for name, kind, _, _ in ARGUMENTS if kind is bool} | {'optim_use_lbfgs'}
+        # the parser's own switches, by the name they are written with (``--optim_use_lbfgs`` stores into ``optim_use_adam``)
+        flags = {a.option_strings[-1].lstrip('-') for a in p._actions if a.nargs == 0 and isinstance(a.const, bool)}
         for k, v in read_config(pre.config):
-            if k in IGNORED_KEYS:
+            if k in ignored_keys:
                 ignored.append(k)
                 continue
             if k in flags:
@@ -415,7 +419,7 @@ def parse_cfg(argv=None):
                 v = ' '.join(s.strip().strip('\'"') for s in v[1:-1].split(','))
             file_args += ['--' + k] + (v.split() if known[k].nargs in ('+', '*') else [v.strip('\'"')])
     cfg = vars(p.parse_args(file_args + argv))
-    if cfg['agent_types'] is not None:
+    if cfg.get('agent_types') is not None:
         cfg['num_classes'] = len(cfg['agent_types'])
     return cfg, ignored
 
