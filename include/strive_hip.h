@@ -974,6 +974,63 @@ int strive_adam_flat(float* p, const float* g, float* m, float* v, int64_t n, do
                      double weight_decay, double bc1, double bc2, const int64_t* seg_off, int32_t nseg, float* seg_absmax,
                      strive_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Scenario pictures
+ * ---------------------------------------------------------------------------------------------- */
+
+/* F pictures of a map crop with cars, trajectories and markers in one launch, no host synchronisation: what the reference draws
+ * with one matplotlib figure per picture (reference src/datasets/nuscenes_utils.py:655-702 viz_map_crop, :717-731
+ * render_map_observation, :733-835 render_obj_observation, :837-853 plot_box / plot_car; called from reference
+ * src/viz_scenario_dir.py:53-107 and reference src/eval_adv_gen.py:537-640).  out: (F, L, L, 3) uint8 RGB, row 0 at the top.
+ *
+ * Frame: the crop's pixel frame of objs2crop (reference src/datasets/map_env.py:231-254): x along the crop's first axis, y along
+ * its second, y up.  Pixel (row, col) is the square [col, col + 1] x [L - 1 - row, L - row].  matplotlib's half-pixel offset
+ * between imshow's pixel centres and xlim(0, L) is NOT reproduced.  Only square pictures: W must equal L (the reference's xlim /
+ * ylim mix the axes otherwise); anything else is an error.
+ *
+ * Background: white, then the map's layers in channel order, c += (v_i alpha_i)(col_i - c) with v_i the raster byte that
+ * get_map_crop_pos(pose, mapix, bounds, L, L) holds at [i, col, L - 1 - row] (imshow(x[i].T, origin='lower')); the gather is the
+ * crop's, bit for bit, the crop itself is not materialised.  The bounds enter as the crop's own fp32 tables: lin (NB, 2, L) holds
+ * torch.linspace(b[0], b[2], L) then torch.linspace(b[1], b[3], L) for NB sets of bounds, lin_ix (F) picks a picture's set.
+ * layer_rgb / layer_alpha: the reference's colour list (darkgray, coral, orange, gold, lightblue, lightblue; 1, .6, .6, .6, 1, .5);
+ * a map of more than STRIVE_RENDER_MAX_LAYERS layers is an error.  no_map[f] != 0: white background.
+ *
+ * Primitives: picture f draws prims[prim_range[2f] .. prim_range[2f+1]) in table order.  A record is STRIVE_RENDER_PRIM_FLOATS
+ * fp32 words (the table 16-byte aligned):
+ *   [0] kind (int32 bits)   [1] cx  [2] cy   [3] hx  [4] hy   [5] l (car) or diameter (disc)  [6] w
+ *   [7..9] RGB in [0, 1]   [10] alpha   [11] stroke width: the car's outline, the polyline   [12] stroke width of the car's heading
+ *   [13] [14] vertex range [begin, end) into verts (NV, 2) (int32 bits, polyline)   [15] unused
+ * THE COVERAGE RULE IS THIS LIBRARY'S OWN (as strive_map_rasterize's is; Agg's anti-aliasing is not reproduced): coverage of a
+ * shape on a pixel = the number of the 4 x 4 regular sub-samples at offsets (k + 1/2)/4 that lie in the shape (boundary included)
+ * / 16; blend c += (alpha cov)(col - c) in fp32; stored byte rint(255 c), clamped.  No atomics; a pixel's bytes depend only on
+ * its own picture's inputs.
+ *   car       with (u, v) the sub-sample in the car's frame (heading normalised; zero heading = (1, 0)): fill |u| <= l/2 and
+ *             |v| <= w/2 in RGB; outline in black, |u| <= l/2 + e and |v| <= w/2 + e and not (|u| < l/2 - e and |v| < w/2 - e),
+ *             e = [11]/2; heading stroke in black, -h <= u <= l/2 + h and |v| <= h, h = [12]/2.  Three blends with the car's alpha.
+ *   polyline  the union of the capsules of radius [11]/2 around consecutive vertices (round caps and joins), blended ONCE.
+ *   disc      distance to (cx, cy) <= [5]/2; every disc is blended on its own.
+ * A primitive with a NaN in its geometry, or a polyline of fewer than 2 vertices, draws nothing. */
+#define STRIVE_RENDER_MAX_LAYERS 6
+#define STRIVE_RENDER_PRIM_FLOATS 16
+#define STRIVE_RENDER_CAR 0
+#define STRIVE_RENDER_POLYLINE 1
+#define STRIVE_RENDER_DISC 2
+typedef struct StriveRenderJob {
+    const float* pose;            /* (F, 4) crop pose x, y, hx, hy (unnormalised) */
+    const int32_t* mapix;         /* (F) */
+    const float* lin;             /* (NB, 2, L) */
+    const int32_t* lin_ix;        /* (F) */
+    const int32_t* prim_range;    /* (F, 2) */
+    const int32_t* no_map;        /* (F) */
+    const float* prims;           /* (NP, STRIVE_RENDER_PRIM_FLOATS) */
+    const float* verts;           /* (NV, 2) */
+    int32_t F, L, W, NP, NV, reserved;
+    float layer_rgb[STRIVE_RENDER_MAX_LAYERS * 3];
+    float layer_alpha[STRIVE_RENDER_MAX_LAYERS];
+} StriveRenderJob;
+
+int strive_render_pictures(const StriveMap* map, const StriveRenderJob* job, uint8_t* out, strive_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -140,6 +140,13 @@ class StriveSceneTables(C.Structure):
                 ('accel', C.c_void_p), ('is_vis', C.c_void_p), ('kept', C.c_void_p)]
 
 
+class StriveRenderJob(C.Structure):
+    _fields_ = [('pose', C.c_void_p), ('mapix', C.c_void_p), ('lin', C.c_void_p), ('lin_ix', C.c_void_p), ('prim_range', C.c_void_p),
+                ('no_map', C.c_void_p), ('prims', C.c_void_p), ('verts', C.c_void_p),
+                ('F', C.c_int32), ('L', C.c_int32), ('W', C.c_int32), ('NP', C.c_int32), ('NV', C.c_int32), ('reserved', C.c_int32),
+                ('layer_rgb', C.c_float * 18), ('layer_alpha', C.c_float * 6)]
+
+
 class StriveNorm(C.Structure):
     _fields_ = [('state_mean', C.c_float * 6), ('state_std', C.c_float * 6), ('att_mean', C.c_float * 2), ('att_std', C.c_float * 2)]
 
@@ -240,6 +247,7 @@ PROTOTYPES = {
                                               P, P, P, P, P, C.c_int64, P]),
     'strive_adam_flat': (C.c_int, [P, P, P, P, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
                                    C.c_double, P, I, P, P]),
+    'strive_render_pictures': (C.c_int, [C.POINTER(StriveMap), C.POINTER(StriveRenderJob), P, P]),
 }
 
 

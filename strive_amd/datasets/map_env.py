@@ -35,6 +35,12 @@ class NuScenesMapEnv(object):
         """(reference :205-228)"""
         return ops.map_crop(self, pos, mapixes, bounds=bounds, L_=L, W_=W)
 
+    def objs2crop(self, center, obj_center, obj_lw, map_idx, bounds=None, L=None, W=None):
+        """Objects (N, 4) and sizes in the pixel frame of the crop around ``center`` (reference :231-254)."""
+        from .. import render
+        return render.objs2crop(center, obj_center, obj_lw, self.bounds if bounds is None else bounds, self.L if L is None else L,
+                                self.W if W is None else W)
+
 
 # ------------------------------------------------------------------------------------------------------------------------
 # Rasterisation from geometry (reference src/datasets/map_env.py:79-166).  The reference gets polygons / lines AND their
