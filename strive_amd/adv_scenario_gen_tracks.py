@@ -31,9 +31,9 @@ import torch
 
 from . import _lib as L
 from . import ops
-from .eval_common import LIN_MAX, lin_table, pack_env
+from .eval_common import LIN_MAX, check_status, i32, lin_table, model_stats, outputs, pack_env, traj_arg
 from .graph import Batch
-from .refine_traffic_tracks import NO_RENDERING, SceneSource, _host_stats, _log, scene_source
+from .refine_traffic_tracks import NO_RENDERING, SceneSource, _log, scene_source
 from .train_traffic import DEVKIT_KEYS
 
 SCREEN_I = ('n_others', 'n_within', 'n_feasible_any_category', 'n_feasible', 'heur_agt', 'heur_t', 'sep_n', 'verdict')
@@ -45,17 +45,6 @@ SCREEN_STATUS_TEXT = {2: 'agent offsets leave the arrays', 3: 'map index out of 
                       6: 'a separation line leaves the raster (or has more than 65536 samples)'}
 EGO_STATUS_TEXT = {2: 'agent offsets leave the arrays, or the attacker index is outside 1..n-1', 3: 'map index out of range',
                    4: 'the drivable-area sampling grid of the ego is outside 1..%d samples per axis' % LIN_MAX}
-
-
-def _outputs(out, dev, spec):
-    out = {} if out is None else dict(out)
-    for key, shape, dtype, fill in spec:
-        out.setdefault(key, torch.full(shape, fill, dtype=dtype, device=dev))
-    return out
-
-
-def _i32(t, dev):
-    return torch.as_tensor(t).to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
 
 
 def screen_batch(samples, model, scene_graph, map_env, map_idx, feasibility_thresh, feasibility_time=0, feasibility_vel=0.0,
@@ -77,9 +66,9 @@ def screen_batch(samples, model, scene_graph, map_env, map_idx, feasibility_thre
     dev = smp.device
     lib = ops._lib_for(smp) if lib is None else lib
     NA, NS, FT = int(smp.shape[0]), int(smp.shape[1]), int(smp.shape[2])
-    ptr = _i32(scene_graph.ptr, dev)
+    ptr = i32(scene_graph.ptr, dev)
     B = int(ptr.numel()) - 1
-    mapix = _i32(map_idx, dev)
+    mapix = i32(map_idx, dev, -1)
     if B < 0 or int(mapix.numel()) != B:
         raise ValueError('screen_batch expects ptr (B+1) and map_idx (B)')
     if planner_name not in PLANNER_RULE:
@@ -92,11 +81,11 @@ def screen_batch(samples, model, scene_graph, map_env, map_idx, feasibility_thre
         Tg = int(gt.shape[1])
     alw = None
     if allowed is not None:
-        alw = _i32(allowed, dev)
+        alw = i32(allowed, dev, -1)
         if int(alw.numel()) != NA:
             raise ValueError('screen_batch expects allowed (NA)')
     inf = float('inf')
-    out = _outputs(out, dev, [('feasible', (NA,), torch.int32, 0), ('within', (NA,), torch.int32, 0), ('step', (NA,), torch.int32, -1),
+    out = outputs(out, dev, [('feasible', (NA,), torch.int32, 0), ('within', (NA,), torch.int32, 0), ('step', (NA,), torch.int32, -1),
                               ('best_samp', (NA,), torch.int32, -1), ('sep_zero', (NA,), torch.int32, 0),
                               ('dist', (NA,), torch.float64, inf), ('max_vel', (NA,), torch.float64, float('nan')),
                               ('out_i', (B, len(SCREEN_I)), torch.int32, 0), ('out_d', (B, len(SCREEN_D)), torch.float64, float('nan')),
@@ -105,7 +94,7 @@ def screen_batch(samples, model, scene_graph, map_env, map_idx, feasibility_thre
         return out
     if NA == 0:                                        # never hand a NULL pointer to the library
         smp = torch.zeros((1, NS, FT, 4), dtype=torch.float32, device=dev)
-    sm, ss, _, _ = _host_stats(model)
+    sm, ss, _, _ = model_stats(model)
     use_infront = feasibility_infront_min is not None
     lib.call('strive_feasibility_screen', L.ptr(smp), L.ptr(ptr), L.ptr(mapix), None if alw is None else L.ptr(alw),
              None if gt is None else L.ptr(gt), sm, ss, ops._map_pack(pack_env(map_env), dev).ref(), float(feasibility_thresh),
@@ -126,24 +115,19 @@ def ego_verdicts(final_result_traj, model, scene_graph, attack_agt=None, map_env
     ``hit``, ``coll_t`` (NA) int32 (the ego's row: any hit / the first step of the scene), ``out_i`` (B,8) int32 in the order of EGO_I,
     ``grid_d`` (B,2) float64, ``status`` (B) int32 (EGO_STATUS_TEXT; the outputs of such a scene are untouched).
     ``compute_adv_gen_success`` of scene b is ``out_i[b, 2] == 1``; ``compute_sol_success`` is ``out_i[b, 1] == 0 and out_i[b, 4] == 0``."""
-    traj = final_result_traj.detach()
-    if traj.dim() == 4 and traj.shape[1] == 1:
-        traj = traj[:, 0]
-    if traj.dim() != 3 or traj.shape[2] != 4:
-        raise ValueError('ego_verdicts expects final_result_traj (NA,1,T,4)')
-    traj = traj.to(torch.float32).contiguous()
+    traj = traj_arg(final_result_traj, 'ego_verdicts')
     dev = traj.device
     lib = ops._lib_for(traj) if lib is None else lib
     NA, T = int(traj.shape[0]), int(traj.shape[1])
-    ptr = _i32(scene_graph.ptr, dev)
+    ptr = i32(scene_graph.ptr, dev)
     B = int(ptr.numel()) - 1
     want_env = map_env is not None
-    mapix = _i32(map_idx, dev) if want_env else None
-    atk = _i32(attack_agt, dev) if attack_agt is not None else None
+    mapix = i32(map_idx, dev, -1) if want_env else None
+    atk = i32(attack_agt, dev, -1) if attack_agt is not None else None
     if B < 0 or T < 1 or (want_env and int(mapix.numel()) != B) or (atk is not None and int(atk.numel()) != B):
         raise ValueError('ego_verdicts expects ptr (B+1), map_idx (B), attack_agt (B) and T >= 1')
     lw = scene_graph.lw.detach().to(device=dev, dtype=torch.float32).reshape(NA, 2).contiguous()
-    out = _outputs(out, dev, [('hit', (NA,), torch.int32, 0), ('coll_t', (NA,), torch.int32, T),
+    out = outputs(out, dev, [('hit', (NA,), torch.int32, 0), ('coll_t', (NA,), torch.int32, T),
                               ('out_i', (B, len(EGO_I)), torch.int32, 0), ('grid_d', (B, 2), torch.float64, float('nan')),
                               ('status', (B,), torch.int32, 0)])
     if B == 0:
@@ -151,20 +135,12 @@ def ego_verdicts(final_result_traj, model, scene_graph, attack_agt=None, map_env
     if NA == 0:                                        # never hand a NULL pointer to the library
         traj = torch.zeros((1, T, 4), dtype=torch.float32, device=dev)
         lw = torch.zeros((1, 2), dtype=torch.float32, device=dev)
-    sm, ss, am, as_ = _host_stats(model)
+    sm, ss, am, as_ = model_stats(model)
     lib.call('strive_ego_verdicts', L.ptr(traj), L.ptr(ptr), L.ptr(lw), None if atk is None else L.ptr(atk), sm, ss, am, as_,
              int(want_env), ops._map_pack(pack_env(map_env), dev).ref() if want_env else None, L.ptr(mapix) if want_env else None,
              L.ptr(lin_table(dev)) if want_env else None, int(lin_max), B, NA, T, L.ptr(out['hit']), L.ptr(out['coll_t']),
              L.ptr(out['out_i']), L.ptr(out['grid_d']), L.ptr(out['status']), L.stream_ptr(traj))
     return out
-
-
-def check_status(codes, text, what, positions=None):
-    """Raise for the first scene a kernel refused (``codes``: the status vector on the host)."""
-    for b, code in enumerate(codes):
-        if code != 0:
-            raise ValueError('scene %s: %s (status %d of %s)' % (positions[b] if positions is not None else b,
-                                                                 text.get(int(code), 'refused'), code, what))
 
 
 class FeasibilityBatcher(object):

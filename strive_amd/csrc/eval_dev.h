@@ -1,5 +1,8 @@
-// Device functions shared by the evaluation metric kernels (eval_metrics.hip): every formula that more than one metric needs
-// is written here once.  The arithmetic helpers run under `#pragma clang fp contract(off)`: every operation is rounded on its
+// Device functions shared by the evaluation metric kernels (eval_metrics.hip; dataset.hip includes it too): every formula that
+// more than one metric needs is written here once, and so is every step that more than one kernel takes -- a scene's prologue
+// (scene_span), the sampling grid (grid_ratios, sample_grid), the drivable test of a frame (road_samples, wave_off_road, off_road),
+// the pair vote of a wave (wave_pair_vote), the rows of a grid (valid_frames, add_valid_rows), normalised inputs (EvalNorm) -- and
+// the two argument checks the entry points share (eval_map_ok, eval_norm_fill).  The arithmetic helpers run under `#pragma clang fp contract(off)`: every operation is rounded on its
 // own, so a formula gives the same bits whichever kernel asks for it, on the device and in a host build.  The box geometry is
 // the exception: rect_iou_kernel reports its IoU, so it stays under the library's contraction rule as it always was; every
 // other user only compares the IoU with EVAL_IOU_THRESH.
@@ -200,9 +203,47 @@ __device__ __forceinline__ int on_road(const CropFrame& fr, float lwise, float w
     return fr.base[(size_t)py * fr.W + px] != 0 ? 1 : 0;
 }
 
+// row k of the caller's linspace table: fp32 linspace(-1, 1, k) for k = 1, 2, ... one after the other, so row k starts at
+// k (k - 1) / 2.  k <= 0 (no grid) gives the table's start, of which nothing is read.
+__device__ __forceinline__ const float* lin_row(const float* lin_tab, int k) { return lin_tab + (k > 0 ? (size_t)k * (k - 1) / 2 : 0); }
+
+// the drivable test of one frame: `on` of its `cells` grid samples lie on the road; off road is fp32(on) / fp32(cells) < fp32(1 - 0.05)
+__device__ __forceinline__ bool off_road(int on, int cells) { return __fdiv_rn((float)on, (float)cells) < (float)(1.0 - 0.05); }
+
+// road_samples: how many of the samples first, first + stride, ... of the L x W grid (L, W >= 1; sample c: row c / W, column c % W) of the
+// frame `pose` (no NaN) of a vehicle of size lw lie on the road of map m.  Integer counts: the order of the samples does not matter.
+// (Row and column are carried from sample to sample -- a stride is di rows and dj < W columns -- so the loop holds no division.)
+__device__ __forceinline__ int road_samples(const StriveMap& map, int m, const float* pose, const float* lw, const float* lin_tab,
+                                            int L, int W, int first, int stride) {
+    const CropFrame fr = map_frame(map, m, pose);
+    const float* lin_l = lin_row(lin_tab, L);
+    const float* lin_w = lin_row(lin_tab, W);
+    const int di = stride / W, dj = stride - di * W;
+    int i = first / W, j = first - i * W, on = 0;
+    for (int c = first; c < L * W; c += stride) {
+        on += on_road(fr, grid_coord(lin_l[i], lw[0]), grid_coord(lin_w[j], lw[1]));
+        i += di;
+        j += dj;
+        if (j >= W) {
+            j -= W;
+            ++i;
+        }
+    }
+    return on;
+}
+
+// wave_off_road: the drivable test of one frame by ONE WAVE: its lanes stride over the samples (road_samples) and add their counts,
+// so every lane returns the same answer (L, W >= 1).
+__device__ __forceinline__ bool wave_off_road(const StriveMap& map, int m, const float* pose, const float* lw, const float* lin_tab,
+                                              int L, int W, int lane) {
+    int on = road_samples(map, m, pose, lw, lin_tab, L, W, lane, 64);
+    for (int k = 32; k >= 1; k >>= 1) on += __shfl_xor(on, k);
+    return off_road(on, L * W);
+}
+
 // Sampling grid of check_on_layer from `rows` valid rows with the sums sl, sw of their vehicle sizes: the mean size and its
-// ratio to mean(dx) over all entries of the map's dx, length then width (L = rint(ratio[0]), W likewise; the range rule is the
-// caller's).  false, and nothing written, without a valid row.
+// ratio to mean(dx) over all entries of the map's dx, length then width (L = rint(ratio[0]), W likewise: sample_grid below, or
+// the caller's own rule).  false, and nothing written, without a valid row.
 __device__ __forceinline__ bool grid_ratios(long long rows, double sl, double sw, const StriveMap& map, double mean[2], double ratio[2]) {
 #pragma clang fp contract(off)
     if (rows <= 0) return false;
@@ -213,5 +254,120 @@ __device__ __forceinline__ bool grid_ratios(long long rows, double sl, double sw
     mean[1] = sw / (double)rows;
     ratio[0] = mean[0] / mdx;
     ratio[1] = mean[1] / mdx;
+    return true;
+}
+
+// sample_grid: L and W of the sampling grid on top of grid_ratios, as the kernels that serve ONE call of check_on_layer form it:
+// rint of the two ratios, each inside what the caller's linspace table holds (1..lin_max).  Without a valid row there is no grid:
+// L = W = 0, mean and ratio untouched, true.  false: an axis is outside the table (its size is then -1) and the caller refuses
+// the scene with status 4.
+__device__ __forceinline__ bool sample_grid(long long rows, double sl, double sw, const StriveMap& map, int lin_max, double mean[2],
+                                            double ratio[2], int& L, int& W) {
+    L = W = 0;
+    if (!grid_ratios(rows, sl, sw, map, mean, ratio)) return true;
+    const double ql = rint(ratio[0]), qw = rint(ratio[1]);
+    L = (ql >= 1.0 && ql <= (double)lin_max) ? (int)ql : -1;
+    W = (qw >= 1.0 && qw <= (double)lin_max) ? (int)qw : -1;
+    return L > 0 && W > 0;
+}
+
+// ---- normalised inputs: the statistics of the two MeanStdNormalizers, and v * std + mean in fp32 (unnorm1) as the reference's
+// unnormalize forms it ----
+struct EvalNorm { float sm[4], ss[4], am[2], asd[2]; };     // state mean / std (x, y, hcos, hsin), attribute mean / std (l, w)
+
+__device__ __forceinline__ void unnorm_pose(const EvalNorm& N, const float* p, float u[4]) {
+    for (int c = 0; c < 4; ++c) u[c] = unnorm1(p[c], N.sm[c], N.ss[c]);
+}
+
+// the size of agent ag of the normalised sizes lw (., 2)
+__device__ __forceinline__ void unnorm_lw(const EvalNorm& N, const float* lw, int ag, float u[2]) {
+    u[0] = unnorm1(lw[(size_t)ag * 2 + 0], N.am[0], N.asd[0]);
+    u[1] = unnorm1(lw[(size_t)ag * 2 + 1], N.am[1], N.asd[1]);
+}
+
+// valid_frames: how many of the `frames` poses of tr hold no NaN after unnormalising (the rows check_on_layer keeps)
+__device__ __forceinline__ int valid_frames(const EvalNorm& N, const float* tr, size_t frames) {
+    int c = 0;
+    for (size_t f = 0; f < frames; ++f) {
+        float u[4];
+        unnorm_pose(N, tr + f * 4, u);
+        c += nan4(u) ? 0 : 1;
+    }
+    return c;
+}
+
+// add_valid_rows: agent ag with the trajectory tr enters a grid's row count and size sums with count * size (not at all without
+// a valid frame: its size may be anything)
+__device__ __forceinline__ void add_valid_rows(const EvalNorm& N, const float* tr, size_t frames, const float* lw, int ag,
+                                               long long& cnt, double& sl, double& sw) {
+#pragma clang fp contract(off)
+    const int c = valid_frames(N, tr, frames);
+    if (c <= 0) return;
+    float lwu[2];
+    unnorm_lw(N, lw, ag, lwu);
+    cnt += c;
+    sl += (double)c * (double)lwu[0];
+    sw += (double)c * (double)lwu[1];
+}
+
+// ---- the prologue of a scene: its agents and whether the kernel may touch them ----
+__device__ __forceinline__ bool map_index_ok(int m, int M) { return m >= 0 && m < M; }      // M: the map set's StriveMap.M
+
+// scene_span: the agents [a0, a0 + n) of scene b from the offsets ptr (B+1) and the scene's status: 2 when they leave the NA rows
+// or n < 1 (nothing of the scene may be read), else, where the kernel asks for a map (mapix given), map_code for a map index
+// outside the M maps, else 0.  Uniform over the workgroup.
+__device__ __forceinline__ int scene_span(const int32_t* ptr, int b, int NA, int& a0, int& n, const int32_t* mapix = nullptr,
+                                          int M = 0, int map_code = 0) {
+    a0 = ptr[b];
+    const int a1 = ptr[b + 1];
+    n = a1 - a0;
+    if (a0 < 0 || n <= 0 || a1 > NA) return 2;
+    if (mapix && !map_index_ok(mapix[b], M)) return map_code;
+    return 0;
+}
+
+// wave_pair_vote: one agent against the agents that follow it, by ONE WAVE.  pi (T,4) is the agent's trajectory and lwi its
+// unnormalised size; the other agents' trajectories start at pj, jstride floats apart, their normalised sizes at lwj.  The lanes
+// stride over the items e = dj * T + t (other agent dj, step t), test the two boxes of the step (REJECT: boxes_apart first, which
+// decides the same and spares the clip; then boxes_hit, for which a frame with a NaN is no hit) and vote.  Returns the lowest
+// hitting item of the first 64 that hold one -- for a single other agent the first step of contact -- or `items` without a hit; the
+// same value in every lane.
+template <bool REJECT>
+__device__ __forceinline__ int wave_pair_vote(const EvalNorm& N, const float* pi, const float* lwi, const float* pj, size_t jstride,
+                                              const float* lwj, int items, int T, int lane) {
+    for (int base = 0; base < items; base += 64) {
+        const int e = base + lane;
+        bool h = false;
+        if (e < items) {
+            const int dj = e / T, t = e - dj * T;
+            float u[4], v[4], lwv[2];
+            unnorm_pose(N, pi + (size_t)t * 4, u);
+            unnorm_pose(N, pj + (size_t)dj * jstride + (size_t)t * 4, v);
+            unnorm_lw(N, lwj, dj, lwv);
+            h = !(REJECT && boxes_apart(u, lwi, v, lwv)) && boxes_hit(u, lwi, v, lwv);
+        }
+        const unsigned long long m = __ballot(h ? 1 : 0);
+        if (m != 0ull) return base + __ffsll((long long)m) - 1;
+    }
+    return items;
+}
+
+// ---- host side: the argument checks the entry points share ----
+static inline bool eval_map_ok(const StriveMap* map) {
+    return map && map->raster && map->dx && map->M >= 1 && map->C >= 1 && map->H >= 1 && map->W >= 1;
+}
+
+// the normaliser statistics from the entry point's four host pointers; false, and nothing written, if one is missing
+static inline bool eval_norm_fill(EvalNorm& N, const float* state_mean4, const float* state_std4, const float* att_mean2,
+                                  const float* att_std2) {
+    if (!state_mean4 || !state_std4 || !att_mean2 || !att_std2) return false;
+    for (int c = 0; c < 4; ++c) {
+        N.sm[c] = state_mean4[c];
+        N.ss[c] = state_std4[c];
+    }
+    for (int c = 0; c < 2; ++c) {
+        N.am[c] = att_mean2[c];
+        N.asd[c] = att_std2[c];
+    }
     return true;
 }

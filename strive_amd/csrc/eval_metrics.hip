@@ -1,6 +1,9 @@
 // Evaluation metrics: the rotated-box IoU, the three batched evaluation kernels (planner, adversarial scenarios, traffic model)
-// and the k-means step of the scenario clustering.  float64 code that no optimisation loop calls; the formulas the metrics
-// share live in eval_dev.h.
+// the verdict and screening kernels of the drivers, and the k-means step of the scenario clustering.  float64 code that no
+// optimisation loop calls; the formulas and the steps the kernels share live in eval_dev.h and are named here where they are used:
+// scene_span (a scene's agents and status 2 / 3), sample_grid on grid_ratios (the sampling grid of check_on_layer), road_samples /
+// wave_off_road / off_road (the drivable test of a frame), wave_pair_vote (one agent against the agents after it), valid_frames /
+// add_valid_rows (the rows a grid is formed from), unnorm_pose / unnorm_lw on EvalNorm (normalised inputs).
 #include "eval_dev.h"
 
 // =============================================================================================
@@ -51,8 +54,9 @@ __global__ __launch_bounds__(256) void planner_eval_kernel(const double* __restr
                                                              int32_t* __restrict__ status) {
     __shared__ int s_key;
     const int b = blockIdx.x, tid = threadIdx.x;
-    const int a0 = ptr[b], n = ptr[b + 1] - a0, TO = T * scale;
-    if (n <= 0 || a0 < 0 || a0 + n > NR) {
+    const int TO = T * scale;
+    int a0, n;
+    if (scene_span(ptr, b, NR, a0, n) != 0) {
         if (tid == 0) status[b] = n == 0 ? 1 : 2;        // 2: ptr does not lie inside ``others`` (nothing is read)
         return;
     }
@@ -140,7 +144,8 @@ extern "C" int strive_planner_eval_metrics(const double* plan, const float* othe
 //      L = round(mean_l / mean(dx)), W likewise, the mean of lw over the valid (agent, step) rows of the scene (the reference's
 //      expanded tensor), formed here in float64 from the per-agent frame counts; samples are (linspace(-1,1,L) * l) / 2 in
 //      fp32 from the caller's table, pixels by crop_dev.h (fp64 divide, round half even, out of bounds -> pixel (0,0)); a
-//      frame is off road when fp32(count) / fp32(L*W) < fp32(1 - 0.05).
+//      frame is off road when fp32(count) / fp32(L*W) < fp32(1 - 0.05).  (sample_grid; one thread per frame walks road_samples
+//      and asks off_road.)
 //   4. compute_accels (:323-337) over [0, CT): the attacker when CT > 2; the others' series concatenated in agent order.
 //   5. log_normal (src/losses/common.py:26-42) of the attacker's latent row and of the others' rows.
 //   6. planner fit over [0, CT): position error, angle between the unit headings (dot product clamped to [-1, 1]).
@@ -181,13 +186,15 @@ __global__ __launch_bounds__(256) void scenario_eval_kernel(ScenarioEvalArgs A, 
     __shared__ unsigned char s_pi[SE_MAX_PAIRS], s_pj[SE_MAX_PAIRS];
     const double kNaN = eval_nan();
     const int b = blockIdx.x, tid = threadIdx.x, T = A.T;
-    const int a0 = A.ptr[b], n = A.ptr[b + 1] - a0, nO = n - 1;
-    int st = 0;
-    if (n <= 0 || a0 < 0 || a0 + n > A.NA) st = 2;
-    else if (n == 1) st = 1;
-    else if (nO > SE_MAX_OTHERS) st = 3;
-    else if (A.atk_agt[b] < 0 || A.atk_agt[b] >= n) st = 2;
-    else if (A.has_map && (A.mapix[b] < 0 || A.mapix[b] >= map.M)) st = 2;
+    int a0, n;
+    int st = scene_span(A.ptr, b, A.NA, a0, n);               // (the map index comes last: a scene of the ego alone has status 1)
+    const int nO = n - 1;
+    if (st == 0) {
+        if (n == 1) st = 1;
+        else if (nO > SE_MAX_OTHERS) st = 3;
+        else if (A.atk_agt[b] < 0 || A.atk_agt[b] >= n) st = 2;
+        else if (A.has_map && !map_index_ok(A.mapix[b], map.M)) st = 2;
+    }
     if (st != 0) {
         if (tid == 0) A.status[b] = st;
         return;
@@ -261,14 +268,9 @@ __global__ __launch_bounds__(256) void scenario_eval_kernel(ScenarioEvalArgs A, 
                 sl += (double)s_cnt[a] * (double)lw[a * 2 + 0];
                 sw += (double)s_cnt[a] * (double)lw[a * 2 + 1];
             }
-            int L = 0, W = 0;
+            int L, W;
             double mean[2] = {kNaN, kNaN}, ratio[2];
-            if (grid_ratios(tot, sl, sw, map, mean, ratio)) {
-                const double ql = rint(ratio[0]), qw = rint(ratio[1]);
-                L = (ql >= 1.0 && ql <= (double)A.lin_max) ? (int)ql : -1;
-                W = (qw >= 1.0 && qw <= (double)A.lin_max) ? (int)qw : -1;
-                if (L < 0 || W < 0) s_env_ok = 0;
-            }
+            if (!sample_grid(tot, sl, sw, map, A.lin_max, mean, ratio, L, W)) s_env_ok = 0;
             s_L = L;
             s_W = W;
             s_ll[0] = mean[0];                                    // (scratch: s_ll is filled in step 5)
@@ -287,21 +289,11 @@ __global__ __launch_bounds__(256) void scenario_eval_kernel(ScenarioEvalArgs A, 
         env_ml = s_ll[0];
         env_mw = s_ll[1];
         const int m = A.mapix[b];
-        const float* lin_l = A.lin_tab + (size_t)L * (L - 1) / 2;     // linspace(-1, 1, k) starts at k (k - 1) / 2
-        const float* lin_w = A.lin_tab + (size_t)W * (W - 1) / 2;
-        const float thresh = (float)(1.0 - 0.05), area = (float)(L * W);
-        for (int e = tid; L > 0 && e < n * CT; e += 256) {
+        for (int e = tid; L > 0 && e < n * CT; e += 256) {          // (one thread per frame: road_samples without a wave)
             const int a = e / CT, t = e - a * CT;
             const float* p = fut + ((size_t)a * T + t) * 4;
             if (nan4(p)) continue;
-            const CropFrame fr = map_frame(map, m, p);
-            const float ls = lw[a * 2 + 0], ws = lw[a * 2 + 1];
-            int on = 0;
-            for (int i = 0; i < L; ++i) {
-                const float lwise = grid_coord(lin_l[i], ls);
-                for (int j = 0; j < W; ++j) on += on_road(fr, lwise, grid_coord(lin_w[j], ws));
-            }
-            if (__fdiv_rn((float)on, area) < thresh) atomicOr(&s_env[a], 1);
+            if (off_road(road_samples(map, m, p, lw + a * 2, A.lin_tab, L, W, 0, 1), L * W)) atomicOr(&s_env[a], 1);
         }
         if (tid == 0) {
             env_frames = 0;
@@ -468,7 +460,7 @@ extern "C" int strive_scenario_eval_metrics(const float* fut, const int32_t* ptr
     STRIVE_CHECK_ARG((z && mu && var) || (!z && !mu && !var), "z, mu and var must be given together");
     STRIVE_CHECK_ARG(!z || (D >= 1 && D <= 64), "latent size must be 1..64");
     STRIVE_CHECK_ARG(!map || (mapix && lin_tab && lin_max >= 1), "a map needs mapix and the linspace table");
-    STRIVE_CHECK_ARG(!map || (map->raster && map->dx && map->M >= 1 && map->C >= 1 && map->H >= 1 && map->W >= 1), "bad map");
+    STRIVE_CHECK_ARG(!map || eval_map_ok(map), "bad map");
     STRIVE_CHECK_ARG(T >= 2 && T <= 4096, "T must be 2..4096");
     STRIVE_CHECK_ARG(NA >= 0, "bad NA");
     if (B <= 0) return 0;
@@ -504,15 +496,16 @@ extern "C" int strive_scenario_eval_metrics(const float* fut, const int32_t* ptr
 //   veh  (compute_coll_rate_veh, :465-545): did_collide_veh (NA,NS): agent i overlaps (IoU > 0.02) some agent j > i of the same
 //        scene at some step of sample s; a frame with a NaN in either pose is no hit.  The reference's early exits make
 //        coll_count the number of set flags and the set does not depend on the order of evaluation: ONE WAVE owns a flag, its
-//        lanes stride over (j, t) and vote, lane 0 writes -- no atomics.
+//        lanes stride over (j, t) and vote (wave_pair_vote, here without the centre-distance reject), lane 0 writes -- no atomics.
 //   env  (compute_coll_rate_env, :366-419 -> check_on_layer, src/datasets/nuscenes_utils.py:266-298): did_collide_map (B,NS)
 //        with env_ego_only, else (NA,NS): some valid frame has fp32(count) / fp32(L W) < fp32(0.95) on raster layer 0.  One
 //        wave owns a flag, walks the frames in order, its lanes stride over the L x W samples (crop_dev.h: fp32 grid, float64
-//        divide, round half even, outside -> pixel (0,0)) and add their integer counts.  The grid couples the batch: L =
+//        divide, round half even, outside -> pixel (0,0)) and add their integer counts (wave_off_road).  The grid couples the batch: L =
 //        round(mean_l / mean(dx)), W likewise, mean over the valid (agent, sample, step) rows of the whole call (ego rows only
 //        with env_ego_only), mean(dx) over all entries of the map's dx.  traffic_eval_grid_kernel (one workgroup, launched
-//        first) forms it in float64: a thread adds count * size for the agents tid, tid + 256, ... in that order, one thread adds
-//        the 256 partial sums in thread order.  grid_i = (L, W, valid rows clamped to int32), grid_d = the two ratios before
+//        first) forms it in float64: a thread adds count * size for the agents tid, tid + 256, ... in that order (add_valid_rows),
+//        one thread adds the 256 partial sums in thread order (te_row_sums); on grid_ratios it rounds with a rule of its own, which
+//        saturates and reports where sample_grid refuses.  grid_i = (L, W, valid rows clamped to int32), grid_d = the two ratios before
 //        rounding (NaN without a valid row: then there is no grid and no collision).  With bit 16 of `groups` the caller's grid_i
 //        is used as given and the first launch is skipped.
 //   status (B): 0 written; 2 agent offsets leave the arrays or n < 1; 3 map index out of range; 4 the grid is outside
@@ -529,25 +522,13 @@ extern "C" int strive_scenario_eval_metrics(const float* fut, const int32_t* ptr
 
 struct TrafficEvalArgs {
     const float* pred; const float* gt; const float* vis; const int32_t* ptr; const float* lw;
-    float sm[4], ss[4], am[2], asd[2];
+    EvalNorm nrm;
     const int32_t* mapix; const float* lin_tab; int lin_max;
     int groups, ego_only;
     int B, NA, NS, T, Tg;
     double* pos_err; double* ang_err; double* disp; int32_t* did_veh; int32_t* did_map;
     int32_t* grid_i; double* grid_d; int32_t* status;
 };
-
-// (Args: TrafficEvalArgs or RefineVerdictArgs -- both hold the normaliser statistics sm, ss, am, asd and the sizes lw)
-template <typename Args>
-__device__ __forceinline__ void te_pose(const Args& A, const float* p, float u[4]) {
-    for (int c = 0; c < 4; ++c) u[c] = unnorm1(p[c], A.sm[c], A.ss[c]);
-}
-
-template <typename Args>
-__device__ __forceinline__ void te_lw(const Args& A, int ag, float u[2]) {
-    u[0] = unnorm1(A.lw[(size_t)ag * 2 + 0], A.am[0], A.asd[0]);
-    u[1] = unnorm1(A.lw[(size_t)ag * 2 + 1], A.am[1], A.asd[1]);
-}
 
 // The valid-row count and the two size sums of a sampling grid from the TE_NT per-thread partials: thread 0 adds them in thread
 // order (the totals are valid in thread 0 only; holds a barrier, so the whole workgroup calls it).
@@ -582,26 +563,9 @@ __global__ __launch_bounds__(TE_NT) void traffic_eval_grid_kernel(TrafficEvalArg
     long long cnt = 0;
     double sl = 0.0, sw = 0.0;
     for (int k = tid; k < items; k += TE_NT) {
-        int a = k;
-        if (A.ego_only) {
-            const int a0 = A.ptr[k], a1 = A.ptr[k + 1];
-            if (a0 < 0 || a1 <= a0 || a1 > A.NA) continue;
-            a = a0;
-        }
-        const float* p = A.pred + (size_t)a * frames * 4;
-        int c = 0;
-        for (size_t f = 0; f < frames; ++f) {
-            float u[4];
-            te_pose(A, p + f * 4, u);
-            c += nan4(u) ? 0 : 1;
-        }
-        if (c > 0) {
-            float lwu[2];
-            te_lw(A, a, lwu);
-            cnt += c;
-            sl += (double)c * (double)lwu[0];
-            sw += (double)c * (double)lwu[1];
-        }
+        int a = k, n;
+        if (A.ego_only && scene_span(A.ptr, k, A.NA, a, n) != 0) continue;     // (a: the ego, the scene's first agent)
+        add_valid_rows(A.nrm, A.pred + (size_t)a * frames * 4, frames, A.lw, a, cnt, sl, sw);
     }
     long long tot;
     double tl, tw;
@@ -632,12 +596,10 @@ __global__ __launch_bounds__(TE_NT) void traffic_eval_kernel(TrafficEvalArgs A, 
     const int b = blockIdx.x, part = blockIdx.y, nparts = gridDim.y, tid = threadIdx.x, lane = tid & 63;
     const int wave = part * (TE_NT / 64) + (tid >> 6), nwaves = nparts * (TE_NT / 64);
     const int T = A.T, Tg = A.Tg, NS = A.NS;
-    const int a0 = A.ptr[b], a1 = A.ptr[b + 1], n = a1 - a0;
     const bool env = (A.groups & TE_ENV) != 0;
-    int st = 0, L = 0, W = 0, rows = 0;
-    if (a0 < 0 || n <= 0 || a1 > A.NA) st = 2;
-    else if (env && (A.mapix[b] < 0 || A.mapix[b] >= map.M)) st = 3;
-    else if (env) {
+    int a0, n, L = 0, W = 0, rows = 0;
+    int st = scene_span(A.ptr, b, A.NA, a0, n, env ? A.mapix : nullptr, map.M, 3);
+    if (st == 0 && env) {
         L = A.grid_i[0];
         W = A.grid_i[1];
         rows = A.grid_i[2];
@@ -656,8 +618,8 @@ __global__ __launch_bounds__(TE_NT) void traffic_eval_kernel(TrafficEvalArgs A, 
             double pos = kNaN, deg = kNaN;
             if (A.vis[o] == 1.0f) {
                 float g[4], p[4];
-                te_pose(A, A.gt + o * 6, g);
-                te_pose(A, A.pred + (ag * NS * T + t) * 4, p);
+                unnorm_pose(A.nrm, A.gt + o * 6, g);
+                unnorm_pose(A.nrm, A.pred + (ag * NS * T + t) * 4, p);
                 pose_err(g, p, pos, deg);
                 deg = deg * EVAL_DEG_PER_RAD;
             }
@@ -676,8 +638,8 @@ __global__ __launch_bounds__(TE_NT) void traffic_eval_kernel(TrafficEvalArgs A, 
             double sd = 0.0, sa = 0.0, pos = 0.0, deg = 0.0;
             for (int t = 0; t < Tc; ++t) {
                 float g[4], p[4];
-                te_pose(A, gt + (size_t)t * 6, g);
-                te_pose(A, pr + ((size_t)s * T + t) * 4, p);
+                unnorm_pose(A.nrm, gt + (size_t)t * 6, g);
+                unnorm_pose(A.nrm, pr + ((size_t)s * T + t) * 4, p);
                 pose_err(g, p, pos, deg);
                 deg = deg * EVAL_DEG_PER_RAD;
                 sd += pos;
@@ -694,8 +656,8 @@ __global__ __launch_bounds__(TE_NT) void traffic_eval_kernel(TrafficEvalArgs A, 
             const int s = e / per, r = e - s * per, s2 = r / Tc, t = r - s2 * Tc;
             if (s2 <= s) continue;
             float p[4], q[4];
-            te_pose(A, pr + ((size_t)s * T + t) * 4, p);
-            te_pose(A, pr + ((size_t)s2 * T + t) * 4, q);
+            unnorm_pose(A.nrm, pr + ((size_t)s * T + t) * 4, p);
+            unnorm_pose(A.nrm, pr + ((size_t)s2 * T + t) * 4, q);
             const double ex = (double)p[0] - (double)q[0], ey = (double)p[1] - (double)q[1];
             acc += sqrt(ex * ex + ey * ey);
         }
@@ -720,49 +682,27 @@ __global__ __launch_bounds__(TE_NT) void traffic_eval_kernel(TrafficEvalArgs A, 
             const int i = f / NS, s = f - i * NS;
             const int items = (n - 1 - i) * T;
             float lwi[2];
-            te_lw(A, a0 + i, lwi);
+            unnorm_lw(A.nrm, A.lw, a0 + i, lwi);
+            const size_t jstride = (size_t)NS * T * 4;                       // sample s of the next agent
             const float* pi = A.pred + ((size_t)(a0 + i) * NS + s) * T * 4;
-            bool hit = false;
-            for (int base = 0; base < items && !hit; base += 64) {
-                const int e = base + lane;
-                bool h = false;
-                if (e < items) {
-                    const int dj = e / T, t = e - dj * T, j = i + 1 + dj;
-                    float u[4], v[4], lwj[2];
-                    te_pose(A, pi + (size_t)t * 4, u);
-                    te_pose(A, A.pred + (((size_t)(a0 + j) * NS + s) * T + t) * 4, v);
-                    te_lw(A, a0 + j, lwj);
-                    h = boxes_hit(u, lwi, v, lwj);
-                }
-                hit = __ballot(h ? 1 : 0) != 0ull;
-            }
+            const bool hit = wave_pair_vote<false>(A.nrm, pi, lwi, pi + jstride, jstride, A.lw + (size_t)(a0 + i + 1) * 2, items, T, lane) < items;
             if (lane == 0) A.did_veh[(size_t)(a0 + i) * NS + s] = hit ? 1 : 0;
         }
     }
 
     // ---- env: one wave per (agent, sample) flag, frames in order, lanes over the sampling grid ----
     if (env) {
-        const int nag = A.ego_only ? 1 : n, m = A.mapix[b], cells = L * W;
-        const float* lin_l = A.lin_tab + (size_t)L * (L > 0 ? L - 1 : 0) / 2;     // linspace(-1, 1, k) starts at k (k - 1) / 2
-        const float* lin_w = A.lin_tab + (size_t)W * (W > 0 ? W - 1 : 0) / 2;
-        const float thresh = (float)(1.0 - 0.05), area = (float)cells;
+        const int nag = A.ego_only ? 1 : n, m = A.mapix[b];
         for (int f = wave; f < nag * NS; f += nwaves) {
             const int a = f / NS, s = f - a * NS, ag = a0 + a;
             float lwa[2];
-            te_lw(A, ag, lwa);
+            unnorm_lw(A.nrm, A.lw, ag, lwa);
             bool hit = false;
             for (int t = 0; rows > 0 && t < T && !hit; ++t) {
                 float u[4];
-                te_pose(A, A.pred + (((size_t)ag * NS + s) * T + t) * 4, u);
+                unnorm_pose(A.nrm, A.pred + (((size_t)ag * NS + s) * T + t) * 4, u);
                 if (nan4(u)) continue;
-                const CropFrame fr = map_frame(map, m, u);
-                int on = 0;
-                for (int c = lane; c < cells; c += 64) {
-                    const int i = c / W, j = c - i * W;
-                    on += on_road(fr, grid_coord(lin_l[i], lwa[0]), grid_coord(lin_w[j], lwa[1]));
-                }
-                for (int k = 32; k >= 1; k >>= 1) on += __shfl_xor(on, k);
-                hit = __fdiv_rn((float)on, area) < thresh;
+                hit = wave_off_road(map, m, u, lwa, A.lin_tab, L, W, lane);
             }
             if (lane == 0) A.did_map[(size_t)(A.ego_only ? b : ag) * NS + s] = hit ? 1 : 0;
         }
@@ -778,7 +718,8 @@ extern "C" int strive_traffic_eval_metrics(const float* pred, const float* gt, c
                                            double* pos_err, double* ang_err, double* disp, int32_t* did_veh, int32_t* did_map,
                                            int32_t* grid_i, double* grid_d, int32_t* status, strive_stream_t stream) {
     STRIVE_CHECK_ARG(pred && ptr && lw && status, "null argument");
-    STRIVE_CHECK_ARG(state_mean4_host && state_std4_host && att_mean2_host && att_std2_host, "null normaliser statistics");
+    TrafficEvalArgs A;
+    STRIVE_CHECK_ARG(eval_norm_fill(A.nrm, state_mean4_host, state_std4_host, att_mean2_host, att_std2_host), "null normaliser statistics");
     STRIVE_CHECK_ARG((groups & ~(TE_ERR | TE_DISP | TE_VEH | TE_ENV | TE_GRID_GIVEN)) == 0, "unknown metric group");
     STRIVE_CHECK_ARG(NA >= 0 && NS >= 1 && T >= 1 && Tg >= 1, "bad sizes");
     STRIVE_CHECK_ARG((long long)NA * NS < 0x7fffffffll && (long long)NA * (T > Tg ? T : Tg) < 0x7fffffffll &&
@@ -788,19 +729,10 @@ extern "C" int strive_traffic_eval_metrics(const float* pred, const float* gt, c
     STRIVE_CHECK_ARG(!(groups & TE_VEH) || did_veh, "veh needs its output");
     if (groups & TE_ENV) {
         STRIVE_CHECK_ARG(map && mapix && lin_tab && lin_max >= 1 && did_map && grid_i && grid_d, "env needs a map, mapix, the linspace table and its outputs");
-        STRIVE_CHECK_ARG(map->raster && map->dx && map->M >= 1 && map->C >= 1 && map->H >= 1 && map->W >= 1, "bad map");
+        STRIVE_CHECK_ARG(eval_map_ok(map), "bad map");
     }
     if (B <= 0) return 0;
-    TrafficEvalArgs A;
     A.pred = pred; A.gt = gt; A.vis = vis; A.ptr = ptr; A.lw = lw;
-    for (int c = 0; c < 4; ++c) {
-        A.sm[c] = state_mean4_host[c];
-        A.ss[c] = state_std4_host[c];
-    }
-    for (int c = 0; c < 2; ++c) {
-        A.am[c] = att_mean2_host[c];
-        A.asd[c] = att_std2_host[c];
-    }
     A.mapix = mapix; A.lin_tab = lin_tab; A.lin_max = lin_max;
     A.groups = groups; A.ego_only = env_ego_only ? 1 : 0;
     A.B = B; A.NA = NA; A.NS = NS; A.T = T; A.Tg = Tg;
@@ -828,16 +760,17 @@ extern "C" int strive_traffic_eval_metrics(const float* pred, const float* gt, c
 //   refine_grid_kernel, one workgroup per scene: the scene's status and ITS OWN sampling grid (check_on_layer, reference
 //        src/datasets/nuscenes_utils.py:266-298, forms L = round(mean_l / mean(dx)), W likewise, from the rows of one call, and the
 //        reference calls it per scene): thread t counts the valid frames of the agents t, t + 256, ... in that order and adds
-//        count * size, thread 0 adds the 256 partial sums in thread order (te_row_sums).  A scene without a valid row has no grid:
+//        count * size (add_valid_rows), thread 0 adds the 256 partial sums in thread order (te_row_sums) and forms the grid
+//        (sample_grid).  A scene without a valid row has no grid:
 //        L = W = 0, ratios NaN, no environment collision.  It also writes the scene's row of out_i with both counts 0 and success 1.
 //   refine_verdict_kernel, gridDim.y workgroups per scene: ONE WAVE owns a flag.
 //        did_veh[i] (check_pairwise_veh_coll, reference src/losses/adv_gen_nusc.py:567-623): agent i overlaps (IoU > 0.02) some
 //        agent j > i of its scene at some step; a frame with a NaN in either pose is no hit.  The reference's early exits make
 //        coll_count the number of set flags, and the set does not depend on the order of evaluation: the lanes stride over (j, t),
-//        reject by centre distance (boxes_apart), clip the rest (boxes_hit) and vote.
+//        reject by centre distance (boxes_apart), clip the rest (boxes_hit) and vote (wave_pair_vote).
 //        did_env[a] (compute_coll_rate_env, reference src/losses/traffic_model.py:366-419): some valid frame has fp32(count) /
 //        fp32(L W) < fp32(0.95) on raster layer 0; the wave walks the frames in order, its lanes stride over the L x W samples and
-//        add their integer counts.
+//        add their integer counts (wave_off_road).
 //        Lane 0 writes the flag and, for a set flag, adds 1 to the scene's count and clears its success: integer atomics only, so
 //        a scene's outputs are bit-identical whatever else is in the batch and however many workgroups serve the scene.
 //   out_i (B,8): num_coll_veh, num_traj_veh (= n), env_coll, env_total (= n), success, L, W, valid rows (clamped to int32)
@@ -849,7 +782,7 @@ extern "C" int strive_traffic_eval_metrics(const float* pred, const float* gt, c
 
 struct RefineVerdictArgs {
     const float* traj; const int32_t* ptr; const float* lw;
-    float sm[4], ss[4], am[2], asd[2];
+    EvalNorm nrm;
     const int32_t* mapix; const float* lin_tab; int lin_max;
     int NA, T;
     int32_t* did_veh; int32_t* did_env; int32_t* out_i; double* grid_d; int32_t* status;
@@ -860,46 +793,24 @@ __global__ __launch_bounds__(TE_NT) void refine_grid_kernel(RefineVerdictArgs A,
     __shared__ long long s_cnt[TE_NT];
     __shared__ double s_l[TE_NT], s_w[TE_NT];
     const int b = blockIdx.x, tid = threadIdx.x, T = A.T;
-    const int a0 = A.ptr[b], a1 = A.ptr[b + 1], n = a1 - a0;
-    int st = 0;
-    if (a0 < 0 || n <= 0 || a1 > A.NA) st = 2;
-    else if (A.mapix[b] < 0 || A.mapix[b] >= map.M) st = 3;
+    int a0, n;
+    const int st = scene_span(A.ptr, b, A.NA, a0, n, A.mapix, map.M, 3);
     if (st != 0) {                                           // (uniform over the workgroup: nobody reaches the barrier below)
         if (tid == 0) A.status[b] = st;
         return;
     }
     long long cnt = 0;
     double sl = 0.0, sw = 0.0;
-    for (int a = tid; a < n; a += TE_NT) {
-        const float* p = A.traj + (size_t)(a0 + a) * T * 4;
-        int c = 0;
-        for (int t = 0; t < T; ++t) {
-            float u[4];
-            te_pose(A, p + (size_t)t * 4, u);
-            c += nan4(u) ? 0 : 1;
-        }
-        if (c > 0) {
-            float lwu[2];
-            te_lw(A, a0 + a, lwu);
-            cnt += c;
-            sl += (double)c * (double)lwu[0];
-            sw += (double)c * (double)lwu[1];
-        }
-    }
+    for (int a = tid; a < n; a += TE_NT) add_valid_rows(A.nrm, A.traj + (size_t)(a0 + a) * T * 4, T, A.lw, a0 + a, cnt, sl, sw);
     long long tot;
     double tl, tw;
     te_row_sums(tid, cnt, sl, sw, s_cnt, s_l, s_w, tot, tl, tw);
     if (tid != 0) return;
     double mean[2], ratio[2] = {eval_nan(), eval_nan()};
-    int L = 0, W = 0;
-    if (grid_ratios(tot, tl, tw, map, mean, ratio)) {
-        const double ql = rint(ratio[0]), qw = rint(ratio[1]);
-        if (!(ql >= 1.0 && ql <= (double)A.lin_max && qw >= 1.0 && qw <= (double)A.lin_max)) {
-            A.status[b] = 4;
-            return;
-        }
-        L = (int)ql;
-        W = (int)qw;
+    int L, W;
+    if (!sample_grid(tot, tl, tw, map, A.lin_max, mean, ratio, L, W)) {
+        A.status[b] = 4;
+        return;
     }
     int32_t* oi = A.out_i + (size_t)b * RV_NI;
     oi[0] = 0;
@@ -927,22 +838,10 @@ __global__ __launch_bounds__(TE_NT) void refine_verdict_kernel(RefineVerdictArgs
     for (int i = wave; i < n; i += nwaves) {
         const int items = (n - 1 - i) * T;
         float lwi[2];
-        te_lw(A, a0 + i, lwi);
+        unnorm_lw(A.nrm, A.lw, a0 + i, lwi);
         const float* pi = A.traj + (size_t)(a0 + i) * T * 4;
-        bool hit = false;
-        for (int base = 0; base < items && !hit; base += 64) {
-            const int e = base + lane;
-            bool h = false;
-            if (e < items) {
-                const int dj = e / T, t = e - dj * T, j = i + 1 + dj;
-                float u[4], v[4], lwj[2];
-                te_pose(A, pi + (size_t)t * 4, u);
-                te_pose(A, A.traj + ((size_t)(a0 + j) * T + t) * 4, v);
-                te_lw(A, a0 + j, lwj);
-                h = !boxes_apart(u, lwi, v, lwj) && boxes_hit(u, lwi, v, lwj);
-            }
-            hit = __ballot(h ? 1 : 0) != 0ull;
-        }
+        const size_t jstride = (size_t)T * 4;
+        const bool hit = wave_pair_vote<true>(A.nrm, pi, lwi, pi + jstride, jstride, A.lw + (size_t)(a0 + i + 1) * 2, items, T, lane) < items;
         if (lane == 0) {
             A.did_veh[a0 + i] = hit ? 1 : 0;
             if (hit) {
@@ -954,25 +853,15 @@ __global__ __launch_bounds__(TE_NT) void refine_verdict_kernel(RefineVerdictArgs
 
     // ---- env: one wave per agent flag, frames in order, lanes over the scene's sampling grid ----
     const int L = oi[5], W = oi[6], m = A.mapix[b], cells = L * W;
-    const float* lin_l = A.lin_tab + (size_t)L * (L > 0 ? L - 1 : 0) / 2;         // linspace(-1, 1, k) starts at k (k - 1) / 2
-    const float* lin_w = A.lin_tab + (size_t)W * (W > 0 ? W - 1 : 0) / 2;
-    const float thresh = (float)(1.0 - 0.05), area = (float)cells;
     for (int a = wave; a < n; a += nwaves) {
         float lwa[2];
-        te_lw(A, a0 + a, lwa);
+        unnorm_lw(A.nrm, A.lw, a0 + a, lwa);
         bool hit = false;
         for (int t = 0; cells > 0 && t < T && !hit; ++t) {
             float u[4];
-            te_pose(A, A.traj + ((size_t)(a0 + a) * T + t) * 4, u);
+            unnorm_pose(A.nrm, A.traj + ((size_t)(a0 + a) * T + t) * 4, u);
             if (nan4(u)) continue;
-            const CropFrame fr = map_frame(map, m, u);
-            int on = 0;
-            for (int c = lane; c < cells; c += 64) {
-                const int i = c / W, j = c - i * W;
-                on += on_road(fr, grid_coord(lin_l[i], lwa[0]), grid_coord(lin_w[j], lwa[1]));
-            }
-            for (int k = 32; k >= 1; k >>= 1) on += __shfl_xor(on, k);
-            hit = __fdiv_rn((float)on, area) < thresh;
+            hit = wave_off_road(map, m, u, lwa, A.lin_tab, L, W, lane);
         }
         if (lane == 0) {
             A.did_env[a0 + a] = hit ? 1 : 0;
@@ -990,21 +879,13 @@ extern "C" int strive_refine_verdicts(const float* traj, const int32_t* ptr, con
                                       int32_t NA, int32_t T, int32_t* did_veh, int32_t* did_env, int32_t* out_i, double* grid_d,
                                       int32_t* status, strive_stream_t stream) {
     STRIVE_CHECK_ARG(traj && ptr && lw && did_veh && did_env && out_i && grid_d && status, "null argument");
-    STRIVE_CHECK_ARG(state_mean4_host && state_std4_host && att_mean2_host && att_std2_host, "null normaliser statistics");
+    RefineVerdictArgs A;
+    STRIVE_CHECK_ARG(eval_norm_fill(A.nrm, state_mean4_host, state_std4_host, att_mean2_host, att_std2_host), "null normaliser statistics");
     STRIVE_CHECK_ARG(map && mapix && lin_tab && lin_max >= 1, "the verdicts need a map, mapix and the linspace table");
-    STRIVE_CHECK_ARG(map->raster && map->dx && map->M >= 1 && map->C >= 1 && map->H >= 1 && map->W >= 1, "bad map");
+    STRIVE_CHECK_ARG(eval_map_ok(map), "bad map");
     STRIVE_CHECK_ARG(NA >= 0 && T >= 1 && (long long)NA * T < 0x7fffffffll, "bad sizes");
     if (B <= 0) return 0;
-    RefineVerdictArgs A;
     A.traj = traj; A.ptr = ptr; A.lw = lw;
-    for (int c = 0; c < 4; ++c) {
-        A.sm[c] = state_mean4_host[c];
-        A.ss[c] = state_std4_host[c];
-    }
-    for (int c = 0; c < 2; ++c) {
-        A.am[c] = att_mean2_host[c];
-        A.asd[c] = att_std2_host[c];
-    }
     A.mapix = mapix; A.lin_tab = lin_tab; A.lin_max = lin_max;
     A.NA = NA; A.T = T;
     A.did_veh = did_veh; A.did_env = did_env; A.out_i = out_i; A.grid_d = grid_d; A.status = status;
@@ -1026,10 +907,12 @@ extern "C" int strive_refine_verdicts(const float* traj, const int32_t* ptr, con
 // alone.  traj (NA,T,4) and lw (NA,2) arrive NORMALISED and are unnormalised in fp32 (unnorm1); everything after that is float64.
 // One workgroup of EV_NW waves per scene:
 //   thread 0 forms the scene's status and, if asked, the sampling grid of ITS ego rows alone (compute_coll_rate_env with
-//        ego_only=True on a single scene hands check_on_layer the ego's valid frames and nothing else);
+//        ego_only=True on a single scene hands check_on_layer the ego's valid frames and nothing else: valid_frames, sample_grid);
 //   wave w owns the other agents 1 + w, 1 + w + EV_NW, ...: its lanes take the steps in order, 64 at a time, reject by centre distance
-//        (boxes_apart), clip the rest (boxes_hit) and vote; the lowest set lane of the first non-empty vote is the collision step;
-//   wave w owns the ego frames w, w + EV_NW, ... of the drivable test, its lanes stride over the L x W samples (integer counts);
+//        (boxes_apart), clip the rest (boxes_hit) and vote; the lowest set lane of the first non-empty vote is the collision step
+//        (wave_pair_vote with one other agent);
+//   wave w owns the ego frames w, w + EV_NW, ... of the drivable test, its lanes stride over the L x W samples (integer counts:
+//        wave_off_road);
 //   thread 0 adds the waves' integer counts in wave order.  No atomics at all.
 //   hit (NA), coll_t (NA): per other agent; the ego's row holds the scene's own n_hit > 0 and first_t
 //   out_i (B,8): n_others, n_hit, atk_hit (-1 without an attacker), first_t (T if none), ego_env (-1 if not asked), L, W, valid ego rows
@@ -1042,7 +925,7 @@ extern "C" int strive_refine_verdicts(const float* traj, const int32_t* ptr, con
 
 struct EgoVerdictArgs {
     const float* traj; const int32_t* ptr; const float* lw; const int32_t* atk;
-    float sm[4], ss[4], am[2], asd[2];
+    EvalNorm nrm;
     const int32_t* mapix; const float* lin_tab; int lin_max, want_env;
     int NA, T;
     int32_t* hit; int32_t* coll_t; int32_t* out_i; double* grid_d; int32_t* status;
@@ -1053,36 +936,23 @@ __global__ __launch_bounds__(TE_NT) void ego_verdict_kernel(EgoVerdictArgs A, St
     __shared__ int s_grid[4], s_atk, s_hit[EV_NW], s_first[EV_NW], s_env[EV_NW];
     __shared__ double s_ratio[2];
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, T = A.T;
-    const int a0 = A.ptr[b], a1 = A.ptr[b + 1], n = a1 - a0;
     const int atk = A.atk ? A.atk[b] : -1;
-    int st = 0;
-    if (a0 < 0 || n <= 0 || a1 > A.NA || (atk != -1 && (atk < 1 || atk >= n))) st = 2;
-    else if (A.want_env && (A.mapix[b] < 0 || A.mapix[b] >= map.M)) st = 3;
+    int a0, n;
+    int st = scene_span(A.ptr, b, A.NA, a0, n, A.want_env ? A.mapix : nullptr, map.M, 3);
+    if (st != 2 && atk != -1 && (atk < 1 || atk >= n)) st = 2;        // (a bad attacker index goes before a bad map index)
     if (st != 0) {                                           // (uniform over the workgroup: nobody reaches the barriers below)
         if (tid == 0) A.status[b] = st;
         return;
     }
     float lwe[2];
-    te_lw(A, a0, lwe);
+    unnorm_lw(A.nrm, A.lw, a0, lwe);
     const float* pe = A.traj + (size_t)a0 * T * 4;
     if (tid == 0) {
         int L = 0, W = 0, rows = 0, bad = 0;
         double mean[2], ratio[2] = {eval_nan(), eval_nan()};
         if (A.want_env) {
-            for (int t = 0; t < T; ++t) {
-                float u[4];
-                te_pose(A, pe + (size_t)t * 4, u);
-                rows += nan4(u) ? 0 : 1;
-            }
-            if (grid_ratios(rows, (double)rows * (double)lwe[0], (double)rows * (double)lwe[1], map, mean, ratio)) {
-                const double ql = rint(ratio[0]), qw = rint(ratio[1]);
-                if (ql >= 1.0 && ql <= (double)A.lin_max && qw >= 1.0 && qw <= (double)A.lin_max) {
-                    L = (int)ql;
-                    W = (int)qw;
-                } else {
-                    bad = 1;
-                }
-            }
+            rows = valid_frames(A.nrm, pe, T);
+            bad = sample_grid(rows, (double)rows * (double)lwe[0], (double)rows * (double)lwe[1], map, A.lin_max, mean, ratio, L, W) ? 0 : 1;
         }
         s_grid[0] = bad; s_grid[1] = L; s_grid[2] = W; s_grid[3] = rows;
         s_ratio[0] = ratio[0]; s_ratio[1] = ratio[1];
@@ -1097,22 +967,8 @@ __global__ __launch_bounds__(TE_NT) void ego_verdict_kernel(EgoVerdictArgs A, St
     // ---- the ego against each other agent: one wave per agent, the steps in order ----
     int cnt = 0, first = T;
     for (int j = 1 + wave; j < n; j += EV_NW) {
-        float lwj[2];
-        te_lw(A, a0 + j, lwj);
-        const float* pj = A.traj + (size_t)(a0 + j) * T * 4;
-        int ct = T;
-        for (int base = 0; base < T && ct == T; base += 64) {
-            const int t = base + lane;
-            bool h = false;
-            if (t < T) {
-                float u[4], v[4];
-                te_pose(A, pe + (size_t)t * 4, u);
-                te_pose(A, pj + (size_t)t * 4, v);
-                h = !boxes_apart(u, lwe, v, lwj) && boxes_hit(u, lwe, v, lwj);
-            }
-            const unsigned long long m = __ballot(h ? 1 : 0);
-            if (m != 0ull) ct = base + __ffsll((long long)m) - 1;
-        }
+        // (wave_pair_vote with ONE other agent: its T items are the steps, so the item it returns is the step of the first contact)
+        const int ct = wave_pair_vote<true>(A.nrm, pe, lwe, A.traj + (size_t)(a0 + j) * T * 4, 0, A.lw + (size_t)(a0 + j) * 2, T, T, lane);
         cnt += ct < T ? 1 : 0;
         first = ct < first ? ct : first;
         if (lane == 0) {
@@ -1127,21 +983,11 @@ __global__ __launch_bounds__(TE_NT) void ego_verdict_kernel(EgoVerdictArgs A, St
     int env = 0;
     if (A.want_env && cells > 0) {
         const int m = A.mapix[b];
-        const float* lin_l = A.lin_tab + (size_t)L * (L - 1) / 2;                 // linspace(-1, 1, k) starts at k (k - 1) / 2
-        const float* lin_w = A.lin_tab + (size_t)W * (W - 1) / 2;
-        const float thresh = (float)(1.0 - 0.05), area = (float)cells;
         for (int t = wave; t < T && !env; t += EV_NW) {
             float u[4];
-            te_pose(A, pe + (size_t)t * 4, u);
+            unnorm_pose(A.nrm, pe + (size_t)t * 4, u);
             if (nan4(u)) continue;
-            const CropFrame fr = map_frame(map, m, u);
-            int on = 0;
-            for (int c = lane; c < cells; c += 64) {
-                const int i = c / W, k = c - i * W;
-                on += on_road(fr, grid_coord(lin_l[i], lwe[0]), grid_coord(lin_w[k], lwe[1]));
-            }
-            for (int k = 32; k >= 1; k >>= 1) on += __shfl_xor(on, k);
-            env = __fdiv_rn((float)on, area) < thresh ? 1 : 0;
+            env = wave_off_road(map, m, u, lwe, A.lin_tab, L, W, lane) ? 1 : 0;
         }
     }
     if (lane == 0) {
@@ -1179,21 +1025,13 @@ extern "C" int strive_ego_verdicts(const float* traj, const int32_t* ptr, const 
                                    const float* lin_tab, int32_t lin_max, int32_t B, int32_t NA, int32_t T, int32_t* hit,
                                    int32_t* coll_t, int32_t* out_i, double* grid_d, int32_t* status, strive_stream_t stream) {
     STRIVE_CHECK_ARG(traj && ptr && lw && hit && coll_t && out_i && grid_d && status, "null argument");
-    STRIVE_CHECK_ARG(state_mean4_host && state_std4_host && att_mean2_host && att_std2_host, "null normaliser statistics");
+    EgoVerdictArgs A;
+    STRIVE_CHECK_ARG(eval_norm_fill(A.nrm, state_mean4_host, state_std4_host, att_mean2_host, att_std2_host), "null normaliser statistics");
     STRIVE_CHECK_ARG(!want_env || (map && mapix && lin_tab && lin_max >= 1), "want_env needs a map, mapix and the linspace table");
-    STRIVE_CHECK_ARG(!want_env || (map->raster && map->dx && map->M >= 1 && map->C >= 1 && map->H >= 1 && map->W >= 1), "bad map");
+    STRIVE_CHECK_ARG(!want_env || eval_map_ok(map), "bad map");
     STRIVE_CHECK_ARG(NA >= 0 && T >= 1 && (long long)NA * T < 0x7fffffffll, "bad sizes");
     if (B <= 0) return 0;
-    EgoVerdictArgs A;
     A.traj = traj; A.ptr = ptr; A.lw = lw; A.atk = atk;
-    for (int c = 0; c < 4; ++c) {
-        A.sm[c] = state_mean4_host[c];
-        A.ss[c] = state_std4_host[c];
-    }
-    for (int c = 0; c < 2; ++c) {
-        A.am[c] = att_mean2_host[c];
-        A.asd[c] = att_std2_host[c];
-    }
     A.mapix = mapix; A.lin_tab = lin_tab; A.lin_max = lin_max; A.want_env = want_env ? 1 : 0;
     A.NA = NA; A.T = T;
     A.hit = hit; A.coll_t = coll_t; A.out_i = out_i; A.grid_d = grid_d; A.status = status;
@@ -1233,7 +1071,7 @@ extern "C" int strive_ego_verdicts(const float* traj, const int32_t* ptr, const 
 
 struct FeasScreenArgs {
     const float* samples; const int32_t* ptr; const int32_t* mapix; const int32_t* allowed; const float* gt;
-    float sm[4], ss[4];
+    EvalNorm nrm;             // (sizes are not read: the attribute half holds the identity)
     double thresh, agent_vel, ego_vel, infront_min;
     int t0, use_infront, check_sep, planner_rule;
     int NA, NS, FT, Tg;
@@ -1251,8 +1089,8 @@ __device__ __forceinline__ double fs_inf() { return __longlong_as_double(0x7ff00
 // unnormalised position (and, for the ego, heading) of sample s, step t of the agent whose samples start at p
 __device__ __forceinline__ void fs_xy(const FeasScreenArgs& A, const float* p, int s, int t, float& x, float& y) {
     const float* q = p + ((size_t)s * A.FT + t) * 4;
-    x = unnorm1(q[0], A.sm[0], A.ss[0]);
-    y = unnorm1(q[1], A.sm[1], A.ss[1]);
+    x = unnorm1(q[0], A.nrm.sm[0], A.nrm.ss[0]);
+    y = unnorm1(q[1], A.nrm.sm[1], A.nrm.ss[1]);
 }
 
 // |a - b| of two fp32 points in float64
@@ -1278,7 +1116,7 @@ __device__ __forceinline__ FsBest fs_agent(const FeasScreenArgs& A, const float*
             double d = fs_len(ax, ay, ex, ey);
             if (A.use_infront) {
                 const float* q = ego + ((size_t)s * FT + t) * 4;
-                const double hx = (double)unnorm1(q[2], A.sm[2], A.ss[2]), hy = (double)unnorm1(q[3], A.sm[3], A.ss[3]);
+                const double hx = (double)unnorm1(q[2], A.nrm.sm[2], A.nrm.ss[2]), hy = (double)unnorm1(q[3], A.nrm.sm[3], A.nrm.ss[3]);
                 const double ux = ((double)ax - (double)ex) / d, uy = ((double)ay - (double)ey) / d;
                 const double cossim = ux * hx + uy * hy;
                 if (!(cossim >= A.infront_min)) d = fs_inf();            // (coincident positions: 0 / 0, not in front)
@@ -1342,10 +1180,8 @@ __global__ __launch_bounds__(TE_NT) void feasibility_screen_kernel(FeasScreenArg
     __shared__ int s_bad[FS_NW], s_n[FS_NW], s_out[FS_NW], s_cnt[FS_NW][3], s_ha[FS_NW], s_ht[FS_NW];
     __shared__ double s_ev[FS_NW], s_hd[FS_NW];
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, NS = A.NS, FT = A.FT;
-    const int a0 = A.ptr[b], a1 = A.ptr[b + 1], n = a1 - a0;
-    int st = 0;
-    if (a0 < 0 || n <= 0 || a1 > A.NA) st = 2;
-    else if (A.mapix[b] < 0 || A.mapix[b] >= map.M) st = 3;
+    int a0, n;
+    const int st = scene_span(A.ptr, b, A.NA, a0, n, A.mapix, map.M, 3);
     if (st != 0) {                                           // (uniform over the workgroup: nobody reaches the barriers below)
         if (tid == 0) A.status[b] = st;
         return;
@@ -1357,7 +1193,7 @@ __global__ __launch_bounds__(TE_NT) void feasibility_screen_kernel(FeasScreenArg
     const size_t vals = (size_t)n * NS * FT * 4;
     for (size_t i = tid; i < vals; i += TE_NT) {
         const int c = (int)(i & 3);
-        bad |= fabsf(unnorm1(ego[i], A.sm[c], A.ss[c])) <= 3.4028234663852886e38f ? 0 : 1;
+        bad |= fabsf(unnorm1(ego[i], A.nrm.sm[c], A.nrm.ss[c])) <= 3.4028234663852886e38f ? 0 : 1;
     }
     double ev = 0.0;
     for (int e = tid; e < NS * (FT - 1); e += TE_NT) {
@@ -1473,8 +1309,8 @@ __global__ __launch_bounds__(TE_NT) void feasibility_screen_kernel(FeasScreenArg
         const float* g = A.gt + (size_t)a0 * A.Tg * 4;
         gv = 0.0;
         for (int t = 0; t + 1 < A.Tg; ++t) {
-            const float x0 = unnorm1(g[t * 4 + 0], A.sm[0], A.ss[0]), y0 = unnorm1(g[t * 4 + 1], A.sm[1], A.ss[1]);
-            const float x1 = unnorm1(g[t * 4 + 4], A.sm[0], A.ss[0]), y1 = unnorm1(g[t * 4 + 5], A.sm[1], A.ss[1]);
+            const float x0 = unnorm1(g[t * 4 + 0], A.nrm.sm[0], A.nrm.ss[0]), y0 = unnorm1(g[t * 4 + 1], A.nrm.sm[1], A.nrm.ss[1]);
+            const float x1 = unnorm1(g[t * 4 + 4], A.nrm.sm[0], A.nrm.ss[0]), y1 = unnorm1(g[t * 4 + 5], A.nrm.sm[1], A.nrm.ss[1]);
             const double v = fs_len(x1, y1, x0, y0);
             gv = (gv != gv || v != v) ? (gv + v) : (v > gv ? v : gv);
         }
@@ -1506,7 +1342,7 @@ extern "C" int strive_feasibility_screen(const float* samples, const int32_t* pt
                                          int32_t* out_i, double* out_d, int32_t* status, strive_stream_t stream) {
     STRIVE_CHECK_ARG(samples && ptr && mapix && feasible && within && step && best_samp && dist && sep_zero && max_vel, "null argument");
     STRIVE_CHECK_ARG(out_i && out_d && status && state_mean4_host && state_std4_host, "null argument");
-    STRIVE_CHECK_ARG(map && map->raster && map->dx && map->M >= 1 && map->C >= 1 && map->H >= 1 && map->W >= 1, "bad map");
+    STRIVE_CHECK_ARG(eval_map_ok(map), "bad map");
     STRIVE_CHECK_ARG(NA >= 0 && NS >= 1 && FT >= 2 && (long long)NA * NS * FT < 0x1fffffffll, "bad sizes");
     STRIVE_CHECK_ARG(t0 >= 0 && t0 < FT, "feasibility_time outside the horizon");
     STRIVE_CHECK_ARG(!use_infront || (infront_min >= -1.0 && infront_min <= 1.0), "feasibility_infront_min must lie in [-1, 1]");
@@ -1516,10 +1352,8 @@ extern "C" int strive_feasibility_screen(const float* samples, const int32_t* pt
     if (B <= 0) return 0;
     FeasScreenArgs A;
     A.samples = samples; A.ptr = ptr; A.mapix = mapix; A.allowed = allowed; A.gt = gt;
-    for (int c = 0; c < 4; ++c) {
-        A.sm[c] = state_mean4_host[c];
-        A.ss[c] = state_std4_host[c];
-    }
+    const float att_mean[2] = {0.0f, 0.0f}, att_std[2] = {1.0f, 1.0f};
+    eval_norm_fill(A.nrm, state_mean4_host, state_std4_host, att_mean, att_std);
     A.thresh = thresh; A.agent_vel = agent_vel; A.ego_vel = ego_vel; A.infront_min = infront_min;
     A.t0 = t0; A.use_infront = use_infront ? 1 : 0; A.check_sep = check_sep ? 1 : 0; A.planner_rule = planner_rule;
     A.NA = NA; A.NS = NS; A.FT = FT; A.Tg = Tg;

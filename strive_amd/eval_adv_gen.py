@@ -20,8 +20,7 @@ import torch
 
 from . import _lib as L
 from . import ops
-from .eval_common import LIN_MAX, lin_table, pack_env, scene_jsons
-from .eval_common import lin_table as _lin_table, pack_env as _pack_env          # noqa: F401  (the names these had while they lived here)
+from .eval_common import LIN_MAX, i32, lin_table, pack_env, scene_jsons
 from .utils.scenario_gen import log_metric_sum, log_freq_stat
 
 OUT_I = ('adv_collide', 'coll_t', 'coll_agt', 'atk_agt', 'num_coll_veh', 'num_traj_veh', 'env_coll_atk', 'env_coll_others', 'n_others',
@@ -80,14 +79,13 @@ def scenario_eval_metrics(fut, ptr, lw, atk_agt, dt, z=None, mu=None, var=None, 
     dev = fut.device
     fut = fut.detach().to(torch.float32).contiguous()
     NA, T = int(fut.shape[0]), int(fut.shape[1])
-    ptr = torch.as_tensor(ptr).to(device=dev, dtype=torch.int32).contiguous()
+    ptr = i32(ptr, dev)
     B = int(ptr.numel()) - 1
     if fut.dim() != 3 or fut.shape[2] != 4 or B < 0:
         raise ValueError('scenario_eval_metrics expects fut (NA,T,4) and ptr (B+1)')
-    i32 = lambda v, fill: (torch.full((B,), fill, dtype=torch.int32, device=dev) if v is None
-                           else torch.as_tensor(v).to(device=dev, dtype=torch.int32).reshape(B).contiguous())
+    per_scene = lambda v, fill: torch.full((B,), fill, dtype=torch.int32, device=dev) if v is None else i32(v, dev, B)
     lw = lw.detach().to(device=dev, dtype=torch.float32).reshape(NA, 2).contiguous()
-    atk_agt, want_feat = i32(atk_agt, 1), i32(want_feat, 0)
+    atk_agt, want_feat = per_scene(atk_agt, 1), per_scene(want_feat, 0)
     dt = torch.as_tensor(dt, dtype=torch.float64).to(dev).expand(B).contiguous() if not torch.is_tensor(dt) or dt.dim() == 0 \
         else dt.to(device=dev, dtype=torch.float64).reshape(B).contiguous()
     if (z is None) != (mu is None) or (z is None) != (var is None):
@@ -99,7 +97,7 @@ def scenario_eval_metrics(fut, ptr, lw, atk_agt, dt, z=None, mu=None, var=None, 
     if plan_fit is None:
         plan_fit, has_fit = torch.zeros((max(B, 1), T, 4), dtype=torch.float32, device=dev), None
     plan_fit = plan_fit.detach().to(device=dev, dtype=torch.float32).reshape(-1, T, 4).contiguous()
-    has_fit = i32(has_fit, 0)
+    has_fit = per_scene(has_fit, 0)
     out_i = torch.full((B, len(OUT_I)), -1, dtype=torch.int32, device=dev)
     out_d = torch.full((B, len(OUT_D)), float('nan'), dtype=torch.float64, device=dev)
     status = torch.zeros((B,), dtype=torch.int32, device=dev)
@@ -114,7 +112,7 @@ def scenario_eval_metrics(fut, ptr, lw, atk_agt, dt, z=None, mu=None, var=None, 
     if map_env is not None:
         map_ref = ops._map_pack(pack_env(map_env), dev).ref()
         lin = lin_table(dev)
-        mapix_t = i32(mapix, 0)
+        mapix_t = per_scene(mapix, 0)
     lib.call('strive_scenario_eval_metrics', L.ptr(fut), L.ptr(ptr), L.ptr(lw), L.ptr(atk_agt), L.ptr(dt), L.ptr(z), L.ptr(mu), L.ptr(var),
              Dz, L.ptr(plan_fit), L.ptr(has_fit), map_ref, L.ptr(mapix_t), L.ptr(lin), LIN_MAX, L.ptr(want_feat), B, NA, T,
              L.ptr(out_i), L.ptr(out_d), L.ptr(status), L.stream_ptr(fut))

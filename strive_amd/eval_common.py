@@ -6,7 +6,65 @@ import os
 
 import torch
 
+from . import _lib as L
+
 LIN_MAX = 128                     # largest sampling grid of the drivable-area check along either axis
+
+
+# ------------------------------------------------------------------------------------------------
+# what every wrapper of a metric kernel does with its arguments
+# ------------------------------------------------------------------------------------------------
+
+def traj_arg(traj, who):
+    """The trajectories of a verdict call, (NA,1,T,4) or (NA,T,4), as contiguous fp32 (NA,T,4); ``who`` names the caller in the error."""
+    traj = traj.detach()
+    if traj.dim() == 4 and traj.shape[1] == 1:
+        traj = traj[:, 0]
+    if traj.dim() != 3 or traj.shape[2] != 4:
+        raise ValueError('%s expects final_result_traj (NA,1,T,4)' % who)
+    return traj.to(torch.float32).contiguous()
+
+
+def i32(t, dev, shape=None):
+    """Offsets, map indices or flags as a contiguous int32 tensor on ``dev``, reshaped to ``shape`` if one is given."""
+    t = torch.as_tensor(t).to(device=dev, dtype=torch.int32)
+    return (t if shape is None else t.reshape(shape)).contiguous()
+
+
+def outputs(out, dev, spec):
+    """A copy of the caller's ``out`` dict (or a new one) in which every ``(key, shape, dtype, fill)`` of ``spec`` that the caller did
+    not supply is a new tensor on ``dev`` holding ``fill``."""
+    out = {} if out is None else dict(out)
+    for key, shape, dtype, fill in spec:
+        out.setdefault(key, torch.full(shape, fill, dtype=dtype, device=dev))
+    return out
+
+
+def host_stats(state_normalizer, att_normalizer):
+    """The four ``float[4]`` arguments of an entry point from the two normalisers, converted ONCE (a normaliser built from device
+    tensors would otherwise be read back on every call)."""
+    sn, an = state_normalizer, att_normalizer
+    return (L.f4(sn.mean_vals[:4].tolist()), L.f4(sn.std_vals[:4].tolist()),
+            L.f4(an.mean_vals[:2].tolist() + [0.0, 0.0]), L.f4(an.std_vals[:2].tolist() + [1.0, 1.0]))
+
+
+def model_stats(model):
+    """``host_stats`` of a model's two normalisers, kept on the model until it is given other normalisers."""
+    sn, an = model.get_normalizer(), model.get_att_normalizer()
+    ent = model.__dict__.get('_strive_verdict_stats')
+    if ent is None or ent[0] is not sn or ent[1] is not an:
+        ent = (sn, an, host_stats(sn, an))
+        model.__dict__['_strive_verdict_stats'] = ent
+    return ent[2]
+
+
+def check_status(codes, text, what, positions=None):
+    """Raise for the first scene a kernel refused (``codes``: the status vector on the host; ``text``: the driver's table of the
+    codes; ``what``: the entry point; ``positions``: the scenes' names, else their index in the call)."""
+    for b, code in enumerate(codes):
+        if code != 0:
+            raise ValueError('scene %s: %s (status %d of %s)' % (positions[b] if positions is not None else b,
+                                                                 text.get(int(code), 'refused'), code, what))
 
 
 def scene_jsons(scene_path):

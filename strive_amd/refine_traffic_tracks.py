@@ -29,7 +29,7 @@ import torch
 
 from . import _lib as L
 from . import ops
-from .eval_common import LIN_MAX, lin_table, pack_env
+from .eval_common import LIN_MAX, check_status, i32, lin_table, model_stats, outputs, pack_env, traj_arg
 from .graph import Batch
 from .refine_traffic_optim import refine_traffic_optim
 from .train_traffic import DEVKIT_KEYS, read_config
@@ -54,62 +54,35 @@ def _log(log, line):
 # verdicts
 # ------------------------------------------------------------------------------------------------
 
-def _host_stats(model):
-    """The four ``float[4]`` arguments of the entry point, converted once per (model, normalisers)."""
-    sn, an = model.get_normalizer(), model.get_att_normalizer()
-    ent = model.__dict__.get('_strive_verdict_stats')
-    if ent is None or ent[0] is not sn or ent[1] is not an:
-        ent = (sn, an, (L.f4(sn.mean_vals[:4].tolist()), L.f4(sn.std_vals[:4].tolist()),
-                        L.f4(an.mean_vals[:2].tolist() + [0.0, 0.0]), L.f4(an.std_vals[:2].tolist() + [1.0, 1.0])))
-        model.__dict__['_strive_verdict_stats'] = ent
-    return ent[2]
-
-
 def batch_verdicts(final_result_traj, model, scene_graph, map_env, map_idx, out=None, lib=None, lin_max=LIN_MAX):
     """The collision verdicts of every scene of a batch, each as the reference's ``compute_metrics`` (:84-121) gives them on that
     scene alone: ONE ``strive_refine_verdicts`` call, nothing read back.  ``final_result_traj`` (NA,1,T,4) or (NA,T,4) and
     ``scene_graph.lw`` NORMALISED, ``scene_graph.ptr`` (B+1), ``map_idx`` (B).  Returns tensors on the trajectories' device:
     ``did_veh``, ``did_env`` (NA) int32, ``out_i`` (B,8) int32 in the order of OUT_I, ``grid_d`` (B,2) float64 (the ratios L and W were
     rounded from), ``status`` (B) int32 (STATUS_TEXT; the outputs of such a scene are untouched).  ``out`` supplies output buffers."""
-    traj = final_result_traj.detach()
-    if traj.dim() == 4 and traj.shape[1] == 1:
-        traj = traj[:, 0]
-    if traj.dim() != 3 or traj.shape[2] != 4:
-        raise ValueError('batch_verdicts expects final_result_traj (NA,1,T,4)')
-    traj = traj.to(torch.float32).contiguous()
+    traj = traj_arg(final_result_traj, 'batch_verdicts')
     dev = traj.device
     lib = ops._lib_for(traj) if lib is None else lib
     NA, T = int(traj.shape[0]), int(traj.shape[1])
-    ptr = torch.as_tensor(scene_graph.ptr).to(device=dev, dtype=torch.int32).contiguous()
+    ptr = i32(scene_graph.ptr, dev)
     B = int(ptr.numel()) - 1
-    mapix = torch.as_tensor(map_idx).to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
+    mapix = i32(map_idx, dev, -1)
     if B < 0 or int(mapix.numel()) != B or T < 1:
         raise ValueError('batch_verdicts expects ptr (B+1), map_idx (B) and T >= 1')
     lw = scene_graph.lw.detach().to(device=dev, dtype=torch.float32).reshape(NA, 2).contiguous()
-    out = {} if out is None else dict(out)
-    new = lambda key, shape, dtype, fill: out.setdefault(key, torch.full(shape, fill, dtype=dtype, device=dev))    # noqa: E731
-    new('did_veh', (NA,), torch.int32, 0)
-    new('did_env', (NA,), torch.int32, 0)
-    new('out_i', (B, len(OUT_I)), torch.int32, 0)
-    new('grid_d', (B, 2), torch.float64, float('nan'))
-    new('status', (B,), torch.int32, 0)
+    out = outputs(out, dev, [('did_veh', (NA,), torch.int32, 0), ('did_env', (NA,), torch.int32, 0),
+                             ('out_i', (B, len(OUT_I)), torch.int32, 0), ('grid_d', (B, 2), torch.float64, float('nan')),
+                             ('status', (B,), torch.int32, 0)])
     if B == 0:
         return out
     if NA == 0:                                        # never hand a NULL pointer to the library
         traj = torch.zeros((1, T, 4), dtype=torch.float32, device=dev)
         lw = torch.zeros((1, 2), dtype=torch.float32, device=dev)
-    sm, ss, am, as_ = _host_stats(model)
+    sm, ss, am, as_ = model_stats(model)
     lib.call('strive_refine_verdicts', L.ptr(traj), L.ptr(ptr), L.ptr(lw), sm, ss, am, as_, ops._map_pack(pack_env(map_env), dev).ref(),
              L.ptr(mapix), L.ptr(lin_table(dev)), int(lin_max), B, NA, T, L.ptr(out['did_veh']), L.ptr(out['did_env']),
              L.ptr(out['out_i']), L.ptr(out['grid_d']), L.ptr(out['status']), L.stream_ptr(traj))
     return out
-
-
-def _check_status(codes, positions):
-    for b, code in enumerate(codes):
-        if code != 0:
-            raise ValueError('scene %s: %s (status %d of strive_refine_verdicts)' % (
-                positions[b] if positions is not None else b, STATUS_TEXT.get(int(code), 'refused'), code))
 
 
 def compute_metrics(metrics, freq_metrics_cnt, freq_metrics_total, cur_z, final_result_traj, model, scene_graph, map_env, map_idx,
@@ -120,7 +93,7 @@ def compute_metrics(metrics, freq_metrics_cnt, freq_metrics_total, cur_z, final_
     v = batch_verdicts(final_result_traj, model, scene_graph, map_env, map_idx)
     host = torch.cat([v['out_i'].reshape(-1), v['status']]).cpu().numpy()
     B = int(v['status'].numel())
-    _check_status(host[B * len(OUT_I):].tolist(), None)
+    check_status(host[B * len(OUT_I):].tolist(), STATUS_TEXT, 'strive_refine_verdicts')
     oi = host[:B * len(OUT_I)].reshape(B, len(OUT_I))
     seq_metrics = dict()
     freq_metrics_cnt, freq_metrics_total = log_freq_stat(freq_metrics_cnt, freq_metrics_total, 'veh_coll', int(oi[:, 0].sum()), int(oi[:, 1].sum()))
@@ -313,7 +286,7 @@ def run_one_epoch(data_loader, batch_size, model, map_env, device, out_path, los
         n_oi = B * len(OUT_I)
         out_i, status = ints[:n_oi].reshape(B, len(OUT_I)), ints[n_oi:n_oi + B]
         maps, ptr_host = ints[n_oi + B:n_oi + 2 * B], ints[n_oi + 2 * B:]
-        _check_status(status.tolist(), positions)
+        check_status(status.tolist(), STATUS_TEXT, 'strive_refine_verdicts', positions)
         for b in range(B):               # (pooled as the reference's per-scene log_freq_stat calls pool them)
             log_freq_stat(freq_cnt, freq_total, 'veh_coll', int(out_i[b, 0]), int(out_i[b, 1]))
             log_freq_stat(freq_cnt, freq_total, 'env_coll', int(out_i[b, 2]), int(out_i[b, 3]))

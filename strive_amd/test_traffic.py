@@ -27,21 +27,13 @@ import torch
 
 from . import _lib as L
 from . import ops
-from .eval_common import LIN_MAX, lin_table, pack_env
+from .eval_common import LIN_MAX, host_stats, i32, lin_table, outputs, pack_env
 from .losses.common import log_normal
 
 G_ERR, G_DISP, G_VEH, G_ENV, G_GRID_GIVEN = 1, 2, 4, 8, 16
 DISP_KEYS = ('pos_minADE', 'pos_minFDE', 'ang_minADE', 'ang_minFDE', 'APD')
 STATUS_TEXT = {2: 'agent offsets leave the arrays', 3: 'map index out of range',
                4: 'the drivable-area sampling grid is outside 1..%d samples per axis' % LIN_MAX}
-
-
-def host_stats(state_normalizer, att_normalizer):
-    """The four ``float[4]`` arguments of the entry point from the two normalisers, converted ONCE (a normaliser built from device
-    tensors would otherwise be read back on every call)."""
-    sn, an = state_normalizer, att_normalizer
-    return (L.f4(sn.mean_vals[:4].tolist()), L.f4(sn.std_vals[:4].tolist()),
-            L.f4(an.mean_vals[:2].tolist() + [0.0, 0.0]), L.f4(an.std_vals[:2].tolist() + [1.0, 1.0]))
 
 
 def traffic_eval_metrics(pred, ptr, lw, state_normalizer, att_normalizer, gt=None, vis=None, map_env=None, mapix=None,
@@ -59,7 +51,7 @@ def traffic_eval_metrics(pred, ptr, lw, state_normalizer, att_normalizer, gt=Non
         raise ValueError('traffic_eval_metrics expects pred (NA,NS,T,4)')
     pred = pred.detach().to(torch.float32).contiguous()
     NA, NS, T = int(pred.shape[0]), int(pred.shape[1]), int(pred.shape[2])
-    ptr = torch.as_tensor(ptr).to(device=dev, dtype=torch.int32).contiguous()
+    ptr = i32(ptr, dev)
     B = int(ptr.numel()) - 1
     if B < 0 or NS < 1 or T < 1:
         raise ValueError('traffic_eval_metrics expects ptr (B+1), NS >= 1 and T >= 1')
@@ -78,30 +70,23 @@ def traffic_eval_metrics(pred, ptr, lw, state_normalizer, att_normalizer, gt=Non
         raise ValueError('err compares pred and gt step by step: T %d != Tg %d' % (T, Tg))
     if env and (map_env is None or mapix is None):
         raise ValueError('env needs map_env and mapix')
-    out = {} if out is None else dict(out)
-    new = lambda key, shape, dtype, fill: out.setdefault(key, torch.full(shape, fill, dtype=dtype, device=dev))
     nan = float('nan')
-    if err:
-        new('pos_err', (NA, Tg), torch.float64, nan)
-        new('ang_err', (NA, Tg), torch.float64, nan)
-    if disp:
-        new('disp', (B, 5), torch.float64, nan)
-    if veh:
-        new('did_collide_veh', (NA, NS), torch.int32, 0)
+    spec = [('pos_err', (NA, Tg), torch.float64, nan), ('ang_err', (NA, Tg), torch.float64, nan)] if err else []
+    spec += [('disp', (B, 5), torch.float64, nan)] if disp else []
+    spec += [('did_collide_veh', (NA, NS), torch.int32, 0)] if veh else []
+    spec += [('did_collide_map', (B if env_ego_only else NA, NS), torch.int32, 0), ('grid_i', (3,), torch.int32, 0),
+             ('grid_d', (2,), torch.float64, nan)] if env else []
+    out = outputs(out, dev, spec + [('status', (B,), torch.int32, 0)])
     map_ref = lin = mapix_t = None
     groups = (G_ERR if err else 0) | (G_DISP if disp else 0) | (G_VEH if veh else 0) | (G_ENV if env else 0)
     if env:
-        new('did_collide_map', (B if env_ego_only else NA, NS), torch.int32, 0)
-        new('grid_i', (3,), torch.int32, 0)
-        new('grid_d', (2,), torch.float64, nan)
         if grid is not None:
             groups |= G_GRID_GIVEN
             for i, v in enumerate((int(grid[0]), int(grid[1]), 1)):          # (fills are launches: no staging copy, no synchronisation)
                 out['grid_i'][i:i + 1].fill_(v)
         map_ref = ops._map_pack(pack_env(map_env), dev).ref()
         lin = lin_table(dev)
-        mapix_t = torch.as_tensor(mapix).to(device=dev, dtype=torch.int32).reshape(B).contiguous()
-    new('status', (B,), torch.int32, 0)
+        mapix_t = i32(mapix, dev, B)
     if B == 0 or groups == 0:
         return out
     if NA == 0:                                        # never hand a NULL pointer to the library
