@@ -869,6 +869,20 @@ int strive_planner_rollout(const StrivePlanner* pl, const double* agent_obs, con
 int strive_planner_routes(const StrivePlanner* pl, int32_t mapix, const double* pose4, int32_t maxr, int32_t maxk,
                           int32_t* nroutes, int32_t* nk, double* knots, int32_t* status, strive_stream_t stream);
 
+/* Debug view used by the parity tests: where strive_planner_rollout keeps its tables in the caller's workspace (host only, no
+ * launch).  After a rollout the workspace holds, for ALL planner steps, the other objects' states and presence (update_wstate,
+ * reference src/planners/hardcode_goalcond_nusc.py:601-621), their predicted trajectories and counts (:686-721) and the ego's
+ * poses; and, for the LAST planner step, the ego's route, its stop preference, the speed profiles (gen_sprofiles, :804-826),
+ * their circle centres (:860-882) and the partial gap minima and near-trajectory counts per chunk (:885-897).
+ * out (n_out >= STRIVE_PLANNER_NLAYOUT) int64: byte offsets of  0 wstate (NR,K,4) f64, 1 present (NR,K) i8,
+ * 2 traj (B*K,cap,ENT) f64 [object x, y, l, w, duplicate mask, NT x (x, y, h)], 3 traj_cnt (B*K) i32, 4 scene_bad (B) i32,
+ * 5 route_nk (B) i32, 6 prefer_stop (B) i32, 7 part_cnt (B,NCHUNK) i32, 8 ego (B,8) f64, 9 route (B,5,MAXK) f64,
+ * 10 prof (B,MAXPROF,3) f64 [s1, acc, final distance], 11 circ (B,P,NT,10) f64, 12 part (B,NCHUNK,P,NT) f64,
+ * 13 poses (B,K,4) f64; then 14 the bytes carved, 15 K, 16 cap, 17 ENT, 18 P, 19 NT, 20 nchunk (the chunks per scene the rollout
+ * launches, of which NCHUNK is the stride), 21 MAXK, 22 MAXPROF, 23 NCHUNK. */
+#define STRIVE_PLANNER_NLAYOUT 24
+int strive_planner_workspace_layout(const StrivePlanner* pl, int32_t nstep, int32_t traj_cap, int64_t* out, int32_t n_out);
+
 /* Operator-level views of two building blocks the rollout kernels evaluate in registers (the kernels call the same device
  * functions); used by the parity tests against the reference's own outputs.
  *

@@ -240,6 +240,7 @@ PROTOTYPES = {
     'strive_planner_workspace_bytes': (SZ, [C.POINTER(StrivePlanner), I, I]),
     'strive_planner_rollout': (C.c_int, [C.POINTER(StrivePlanner), P, P, I, P, I, P, I, I, P, P, P, P, SZ, P]),
     'strive_planner_routes': (C.c_int, [C.POINTER(StrivePlanner), I, P, I, I, P, P, P, P, P]),
+    'strive_planner_workspace_layout': (C.c_int, [C.POINTER(StrivePlanner), I, I, P, I]),
     'strive_dataset_post_process': (C.c_int, [C.POINTER(StriveTracks), C.POINTER(StriveMap), C.POINTER(StriveSceneTables), I, C.c_double,
                                               P, P, I, P, SZ, P]),
     'strive_dataset_window_counts': (C.c_int, [C.POINTER(StriveSceneTables), P, I, I, I, I, P, P]),

@@ -1142,6 +1142,18 @@ Layout carve(const StrivePlanner* pl, int nstep, int traj_cap, void* ws, size_t 
     return L;
 }
 
+// threads of the gap kernel's workgroup: one per (profile, time), whole waves
+static int gap_threads_of(int P, int NT) { return ((P * NT + 63) / 64) * 64; }
+
+// chunks per scene: as many as keep ALL (scene, chunk) workgroups of a step resident at once -- a workgroup of P x NT threads
+// is 11 waves at the default 25 x 26, two of them fit a CU, 512 the chip; 36 scenes x 16 chunks = 576 workgroups ran as one full
+// round and a second one of 64.  The rollout and the layout view both ask here.
+static int gap_chunks(int gap_threads, int B) {
+    const int waves = gap_threads / 64, per_cu = 32 / waves < 1 ? 1 : 32 / waves;
+    const int nc = (256 * per_cu) / B;
+    return nc < 4 ? 4 : (nc > NCHUNK ? NCHUNK : nc);
+}
+
 int check_cfg(const StrivePlanner* pl, int nstep, int traj_cap) {
     const StrivePlannerCfg& c = pl->cfg;
     STRIVE_CHECK_ARG(pl->nmaps >= 1 && pl->nmaps <= STRIVE_PLANNER_MAXMAPS, "1..4 maps");
@@ -1186,17 +1198,10 @@ extern "C" int strive_planner_rollout(const StrivePlanner* pl, const double* age
         hipLaunchKernelGGL(planner_world_kernel, dim3((pl->NR + 63) / 64), dim3(64), 0, stream, *pl, w, agent_obs, agent_t, (int)T);
         hipLaunchKernelGGL(planner_routes_kernel, dim3(pl->NR * w.K), dim3(64), 0, stream, *pl, w, status);
     }
-    const int gap_threads = ((w.P * w.NT + 63) / 64) * 64;
+    const int gap_threads = gap_threads_of(w.P, w.NT);
     // one thread per (profile, time) of the risk scores and the circles where that fits (25 x 26 -> 704: one pass)
     const int ego_threads = gap_threads < 256 ? 256 : gap_threads;
-    // chunks per scene: as many as keep ALL (scene, chunk) workgroups of a step resident at once -- a workgroup of P x NT threads
-    // is 11 waves at the default 25 x 26, two of them fit a CU, 512 the chip; 36 scenes x 16 chunks = 576 workgroups ran as one full
-    // round and a second one of 64
-    {
-        const int waves = gap_threads / 64, per_cu = 32 / waves < 1 ? 1 : 32 / waves;
-        const int nc = (256 * per_cu) / (int)pl->B;
-        w.nchunk = nc < 4 ? 4 : (nc > NCHUNK ? NCHUNK : nc);
-    }
+    w.nchunk = gap_chunks(gap_threads, (int)pl->B);
     for (int k = 0; k <= w.K; ++k) {
         hipLaunchKernelGGL(planner_ego_kernel, dim3(pl->B), dim3(ego_threads), 0, stream, *pl, w, k, status);
         if (k < w.K)
@@ -1216,5 +1221,22 @@ extern "C" int strive_planner_routes(const StrivePlanner* pl, int32_t mapix, con
     hipLaunchKernelGGL(planner_routes_debug_kernel, dim3(1), dim3(64), 0, stream, *pl, (int)mapix, pose4, (int)maxr, (int)maxk, nroutes, nk,
                        knots, status);
     STRIVE_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int strive_planner_workspace_layout(const StrivePlanner* pl, int32_t nstep, int32_t traj_cap, int64_t* out, int32_t n_out) {
+    STRIVE_CHECK_ARG(pl && out, "null argument");
+    if (check_cfg(pl, nstep, traj_cap)) return -1;
+    STRIVE_CHECK_ARG(n_out >= STRIVE_PLANNER_NLAYOUT, "out holds fewer than STRIVE_PLANNER_NLAYOUT entries");
+    char* const base = (char*)64;       // (carve's own base for a measuring pass: only differences are used)
+    const Layout L = carve(pl, nstep, traj_cap, nullptr, 0);
+    const Work& w = L.w;
+    const void* tables[14] = {w.wstate, w.present, w.traj, w.traj_cnt, w.scene_bad, w.route_nk, w.prefer_stop, w.part_cnt,
+                              w.ego, w.route, w.prof, w.circ, w.part, w.poses};
+    for (int i = 0; i < 14; ++i) out[i] = (int64_t)((const char*)tables[i] - base);
+    out[14] = (int64_t)L.total;
+    out[15] = w.K; out[16] = w.cap; out[17] = w.ENT; out[18] = w.P; out[19] = w.NT;
+    out[20] = gap_chunks(gap_threads_of(w.P, w.NT), (int)pl->B);
+    out[21] = MAXK; out[22] = MAXPROF; out[23] = NCHUNK;
     return 0;
 }

@@ -30,18 +30,9 @@ os.environ['STRIVE_POISON_WS'] = '1'          # the planner's workspace starts a
 
 @pytest.fixture()
 def emu_ops():
-    import build as emu_build
-    emu = L.StriveLib(emu_build.build(), require_all=True)
-    orig = (ops._lib_for, L.get_lib)
-    ops._lib_for = lambda *tensors: emu           # CPU tensors + the emulated library: test infrastructure only
-    L.get_lib = lambda: emu
-    from util import poison_new_workspaces, nan_empty
-    orig_ws = poison_new_workspaces(ops)          # new scratch buffers start as NaN bytes, not as whatever torch.empty holds
-    orig_empty, torch.empty = torch.empty, nan_empty()      # ... and so does every output allocated with torch.empty
-    yield emu
-    torch.empty = orig_empty
-    ops._workspace = orig_ws
-    ops._lib_for, L.get_lib = orig
+    from planner_worlds import emulated_ops
+    with emulated_ops() as emu:
+        yield emu
 
 
 # ------------------------------------------------------------------------------------------------
