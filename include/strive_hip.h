@@ -1045,6 +1045,88 @@ typedef struct StriveRenderJob {
 
 int strive_render_pictures(const StriveMap* map, const StriveRenderJob* job, uint8_t* out, strive_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Lane graphs built on the device (reference src/datasets/nuscenes_utils.py:28-122: remove_duplicates, process_lanegraph,
+ * process_edges; the Singapore flip of src/datasets/map_env.py:131-144) and the planner's tables of them (StrivePlannerMap).
+ * Input: one map's discretised lanes, in the order nmap.lane + nmap.lane_connector, before any cleaning, and per lane the
+ * `outgoing` / `incoming` lists of nmap.connectivity as lane indices (-1: a token that has no lane).  float64, no contraction.
+ *
+ * THE LENGTH RULE, used for every distance of these entry points (duplicate test, trimming test, edge table, connection
+ * lengths):   |(dx, dy)| = sqrt(fma(dy, dy, dx * dx)).   It is what numpy's np.linalg.norm of a 1-D pair evaluates (BLAS ddot
+ * accumulates with a fused multiply-add); chosen over the unfused sqrt(dx*dx + dy*dy) because it agrees with every edge length
+ * of the reference fixture tests/golden/g25_lane_graph.npz (804 of 804), the unfused sum with 751 of them.
+ *
+ * Rules, in the reference's order:
+ *  1. point i < n-1 of a lane is kept iff |p[i+1] - p[i]| > eps; the last point always;
+ *  2. per lane, for each outgoing lane in list order: if |succ.first - this.last| <= eps, this lane loses its last point (the
+ *     next comparison uses the new last point);
+ *  3. nodes are numbered in lane order.  out list of a node: the next node of its lane, or, on the lane's last node, the first
+ *     nodes of its outgoing lanes in list order.  in list: the previous node, or, on the first node, the last nodes of its
+ *     incoming lanes in list order;
+ *  4. edges in node order, then list order: (x0, y0, dx/d, dy/d, d) and (v0, v1);
+ *  5. with `flip`: xy.y = height - y, edges.y0 = height - y0, edges.dy/d *= -1 (after the edges exist);
+ *  6. connection lengths (StriveLaneNode.len, *_len) from the FINAL positions.
+ * Refusals (the reference's four assertions) are reported in the count record, never by a partly built table.
+ *
+ * Protocol: the count entry point leaves everything but the output tables in the workspace and writes counts[8] (device):
+ * N, M (out connections = edges), MI (in connections), status, offending lane (rules 1, 2) or node (rules 3, 4), the lane of
+ * that node, 0, 0.  The host reads that record back ONCE, allocates, and calls the fill entry point with the same input and
+ * workspace; nothing is read back after the fill.  Results do not depend on the launch geometry.
+ * ---------------------------------------------------------------------------------------------- */
+#define STRIVE_LANE_GRAPH_OK 0
+#define STRIVE_LANE_GRAPH_FIRST_POINT_DROPPED 1   /* rule 1 drops a lane's first point (remove_duplicates' assert kept[0]) */
+#define STRIVE_LANE_GRAPH_LANE_EMPTIED 2          /* rule 2 leaves a lane without a point */
+#define STRIVE_LANE_GRAPH_SHORT_EDGE 3            /* an edge is not longer than eps */
+#define STRIVE_LANE_GRAPH_EDGE_TWICE 4            /* the same (v0, v1) appears twice */
+
+typedef struct StriveLaneGraphIn {
+    const double* pts;            /* (P, 2) every lane's points, lane after lane */
+    const int32_t* lane_ptr;      /* (NL+1) */
+    const int32_t* out_ptr;       /* (NL+1) CSR of the outgoing lists */
+    const int32_t* out_idx;       /* lane index or -1 */
+    const int32_t* in_ptr;        /* (NL+1) CSR of the incoming lists */
+    const int32_t* in_idx;
+    int32_t NL, P, flip, reserved;
+    double eps, height;
+} StriveLaneGraphIn;
+
+typedef struct StriveLaneGraphOut {
+    double* xy;                   /* (N, 2) */
+    StriveLaneNode* succ;         /* (N) */
+    StriveLaneNode* pred;         /* (N) */
+    int32_t* succ_ptr;            /* (N+1) */
+    int32_t* succ_idx;            /* (M) */
+    double* succ_len;             /* (M) */
+    int32_t* pred_ptr;            /* (N+1) */
+    int32_t* pred_idx;            /* (MI) */
+    double* pred_len;             /* (MI) */
+    double* edges;                /* (M, 5) */
+    int32_t* edge_ix;             /* (M, 2) */
+    int32_t N, M, MI, reserved;
+} StriveLaneGraphOut;
+
+size_t strive_lane_graph_workspace_bytes(int32_t NL, int32_t P);
+int strive_lane_graph_count(const StriveLaneGraphIn* in, void* ws, size_t ws_bytes, int32_t* counts, strive_stream_t stream);
+int strive_lane_graph_fill(const StriveLaneGraphIn* in, void* ws, size_t ws_bytes, const StriveLaneGraphOut* out, strive_stream_t stream);
+
+/* Uniform grid over directed edges (x0, y0, unit direction, length) -- StrivePlannerMap's cell_ptr / cell_edges, bit for bit
+ * what the host's edge_grid of strive_amd/planners/hardcode_goalcond_nusc.py builds for get_lane_matches
+ * (reference src/planners/hardcode_goalcond_nusc.py:298-322): p1 = p0 + len*dir (a multiply, then an add), boxes grown by
+ * pad = margin*(1+1e-9) + 1e-6, origin = floor of the minima, cell ranges by floor, every edge listed in every cell its box
+ * touches, ascending by edge id.  The count entry point writes *rec (device); the host reads it back ONCE and passes a host
+ * copy to the fill entry point with cell_ptr (gnx*gny+1) and cell_edges (total).  The fill's workspace is sized for the cells. */
+typedef struct StriveEdgeGridRec {
+    double gx0, gy0;
+    int64_t total;
+    int32_t gnx, gny;             /* 0: the edges do not span a finite grid */
+} StriveEdgeGridRec;
+
+size_t strive_edge_grid_workspace_bytes(int32_t M, int64_t ncell);
+int strive_edge_grid_count(const double* edges, int32_t M, double margin, double cell, void* ws, size_t ws_bytes, StriveEdgeGridRec* rec,
+                           strive_stream_t stream);
+int strive_edge_grid_fill(const double* edges, int32_t M, double margin, double cell, const StriveEdgeGridRec* rec_host, void* ws,
+                          size_t ws_bytes, int32_t* cell_ptr, int32_t* cell_edges, strive_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -147,6 +147,22 @@ class StriveRenderJob(C.Structure):
                 ('layer_rgb', C.c_float * 18), ('layer_alpha', C.c_float * 6)]
 
 
+class StriveLaneGraphIn(C.Structure):
+    _fields_ = [('pts', C.c_void_p), ('lane_ptr', C.c_void_p), ('out_ptr', C.c_void_p), ('out_idx', C.c_void_p), ('in_ptr', C.c_void_p),
+                ('in_idx', C.c_void_p), ('NL', C.c_int32), ('P', C.c_int32), ('flip', C.c_int32), ('reserved', C.c_int32),
+                ('eps', C.c_double), ('height', C.c_double)]
+
+
+class StriveLaneGraphOut(C.Structure):
+    _fields_ = [('xy', C.c_void_p), ('succ', C.c_void_p), ('pred', C.c_void_p), ('succ_ptr', C.c_void_p), ('succ_idx', C.c_void_p),
+                ('succ_len', C.c_void_p), ('pred_ptr', C.c_void_p), ('pred_idx', C.c_void_p), ('pred_len', C.c_void_p),
+                ('edges', C.c_void_p), ('edge_ix', C.c_void_p), ('N', C.c_int32), ('M', C.c_int32), ('MI', C.c_int32), ('reserved', C.c_int32)]
+
+
+class StriveEdgeGridRec(C.Structure):
+    _fields_ = [('gx0', C.c_double), ('gy0', C.c_double), ('total', C.c_int64), ('gnx', C.c_int32), ('gny', C.c_int32)]
+
+
 class StriveNorm(C.Structure):
     _fields_ = [('state_mean', C.c_float * 6), ('state_std', C.c_float * 6), ('att_mean', C.c_float * 2), ('att_std', C.c_float * 2)]
 
@@ -249,6 +265,12 @@ PROTOTYPES = {
     'strive_adam_flat': (C.c_int, [P, P, P, P, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
                                    C.c_double, P, I, P, P]),
     'strive_render_pictures': (C.c_int, [C.POINTER(StriveMap), C.POINTER(StriveRenderJob), P, P]),
+    'strive_lane_graph_workspace_bytes': (SZ, [I, I]),
+    'strive_lane_graph_count': (C.c_int, [C.POINTER(StriveLaneGraphIn), P, SZ, P, P]),
+    'strive_lane_graph_fill': (C.c_int, [C.POINTER(StriveLaneGraphIn), P, SZ, C.POINTER(StriveLaneGraphOut), P]),
+    'strive_edge_grid_workspace_bytes': (SZ, [I, C.c_int64]),
+    'strive_edge_grid_count': (C.c_int, [P, I, C.c_double, C.c_double, P, SZ, P, P]),
+    'strive_edge_grid_fill': (C.c_int, [P, I, C.c_double, C.c_double, C.POINTER(StriveEdgeGridRec), P, SZ, P, P, P]),
 }
 
 

@@ -19,7 +19,8 @@ and the scenario files.  What the reference does once per scene on the host is d
   the files ``eval_adv_gen``, ``cluster_scenarios``, ``eval_planner`` and the dataset's ``scenario_path`` read.  The arguments are the
   reference's, with its defaults, plus ``--tracks`` / ``--scenario_path``, ``--seed``, ``--device``, ``--screen_agents`` and
   ``--on_planner_error``.  ``OUT`` is used as given: the reference appends ``_<unix time>`` to it.  With ``--planner hardcode`` the map
-  environment carries ``synth.make_lane_graph()`` (the reference's ``load_lanegraph``).  Not offered: rendering (``--viz``), wandb,
+  environment carries ``synth.make_lane_graph()`` (the reference's ``load_lanegraph``), or, with ``--maps FILE``, the lane graphs of
+  that maps file, built on the device (datasets/maps.py).  Not offered: rendering (``--viz``), wandb,
   several ranks, and ``init_coll_env``, which the reference computes for its rendering alone.
 """
 import json
@@ -567,6 +568,7 @@ ARGUMENTS = (
     ('num_classes', int, 2, 'number of agent categories when --agent_types is not given'),
     ('tracks', str, None, 'tracks file (datasets/tracks.py) to take the scenes from'),
     ('scenario_path', str, None, 'a directory of scenario files appended to the scenes'),
+    ('maps', str, None, 'a maps file (datasets/maps.py) with the maps the scenes name; default: the synthetic maps'),
     ('seq_interval', int, 10, 'steps from the start of one window of a scene to the start of the next'),
     ('shuffle', bool, False, 'walk the scenes in a random order (drawn from --seed)'),
     ('adv_attack_with', str, None, 'attack with agents of this category only'),
@@ -625,9 +627,10 @@ def main(argv=None, keep_results=False):
         device = torch.device(cfg['device'])
         _log(log, 'Using device %s...' % str(device))
         torch.manual_seed(cfg['seed'])
-        loader, map_env = tracks_loader({k: cfg[k] for k in ('tracks', 'scenario_path', 'num_classes', 'past_len', 'future_len',
-                                                             'seq_interval')}, device)
-        if cfg['planner'] == 'hardcode':            # (the reference's load_lanegraph=(cfg.planner == 'hardcode'))
+        data_cfg = {k: cfg[k] for k in ('tracks', 'scenario_path', 'maps', 'num_classes', 'past_len', 'future_len', 'seq_interval')}
+        # (the reference's load_lanegraph=(cfg.planner == 'hardcode'): a maps file brings its own lane graphs, built on the device)
+        loader, map_env = tracks_loader(dict(data_cfg, load_lanegraph=cfg['planner'] == 'hardcode'), device)
+        if cfg['planner'] == 'hardcode' and cfg['maps'] is None:
             lane_graph = synth.make_lane_graph()
             map_env.lane_graphs = {name: lane_graph for name in map_env.map_list}
         dataset = loader.dataset

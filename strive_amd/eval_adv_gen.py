@@ -483,6 +483,7 @@ def get_parser():
     p.add_argument('--eval_quant', action='store_true', help='quantitative evaluation')
     p.add_argument('--eval_qual', action='store_true', help='qualitative evaluation (rendering; not available)')
     p.add_argument('--map_world', type=str, default=None, choices=['synthetic'], help='map environment with the drivable raster')
+    p.add_argument('--maps', type=str, default=None, help='a maps file (datasets/maps.py) with the maps the scenes name, instead of --map_world')
     p.add_argument('--batch_scenes', type=int, default=256, help='scenes per kernel call')
     p.add_argument('--device', type=str, default='cuda:0')
     return p
@@ -490,11 +491,16 @@ def get_parser():
 
 def main(argv=None):
     cfg = vars(get_parser().parse_args(argv))
-    if cfg['map_world'] is None:
+    from .eval_traffic_tracks import maps_file_env, one_map_source, scenario_map_names
+    one_map_source(cfg, 'map_world')
+    if cfg['map_world'] is None and cfg['maps'] is None:
         raise SystemExit('eval_adv_gen: the nuScenes devkit and data are not available here; a map environment with the drivable '
                          'raster must be supplied from Python (quant_eval(scenarios, cluster_path, cluster_labels, map_env, ...)), or '
                          'use --map_world synthetic')
     os.makedirs(cfg['out'], exist_ok=True)
+    if cfg['maps'] is not None:
+        needed = scenario_map_names(*[os.path.join(cfg['scenarios'], r) for r in ('adv_failed', 'adv_sol_success', 'sol_failed')])
+        return eval_adv_gen(cfg, maps_file_env(cfg['maps'], needed, cfg['device']))
     return eval_adv_gen(cfg, SyntheticMapWorld())
 
 

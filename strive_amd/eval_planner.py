@@ -257,6 +257,7 @@ def get_parser():
     p.add_argument('--eval_replay_planner', action='store_true', help='evaluate the recorded ego trajectory instead of the planner')
     p.add_argument('--batch_scenes', type=int, default=64, help='scenes per planner / metrics call')
     p.add_argument('--lane_world', type=str, default=None, choices=['synthetic'], help='map environment with lane graphs')
+    p.add_argument('--maps', type=str, default=None, help='a maps file (datasets/maps.py) with the maps the scenes name, instead of --lane_world')
     p.add_argument('--dt', type=float, default=0.5, help='time step of the scenarios')
     p.add_argument('--device', type=str, default='cuda:0')
     for k, v in DEF_CONFIG.items():
@@ -271,7 +272,9 @@ def main(argv=None):
     from .planners.planner import PlannerConfig
     from .planners.hardcode_goalcond_nusc import DEF_CONFIG
     cfg = vars(get_parser().parse_args(argv))
-    if cfg['lane_world'] is None:
+    from .eval_traffic_tracks import maps_file_env, one_map_source, scenario_map_names
+    one_map_source(cfg, 'lane_world')
+    if cfg['lane_world'] is None and cfg['maps'] is None:
         raise SystemExit('eval_planner: the nuScenes devkit and data are not available here; a map environment with lane graphs must '
                          'be supplied from Python (run_planner_eval(plan_cfg, loader, map_env, ...)), or use --lane_world synthetic')
     if not cfg['skip_regular'] and cfg['tracks'] is None:
@@ -281,16 +284,26 @@ def main(argv=None):
     os.makedirs(cfg['out'], exist_ok=True)
     with open(os.path.join(cfg['out'], 'plan_cfg.json'), 'w') as f:
         json.dump(plan_cfg_dict, f)
-    if cfg['skip_regular'] or cfg['tracks'] is None:
-        run_planner_eval(PlannerConfig(**plan_cfg_dict), None, SyntheticLaneWorld(), cfg['dt'], cfg['device'], cfg['out'], None, None,
+    regular = not (cfg['skip_regular'] or cfg['tracks'] is None)
+    file_world = None
+    if cfg['maps'] is not None:                  # the maps the scenes were driven on, lane graphs built on the device
+        from .datasets.tracks import load_tracks
+        needed = scenario_map_names(cfg['scenario_dir']) if cfg['scenario_dir'] is not None else []
+        needed += [m for m in (load_tracks(cfg['tracks'])['scene_map'] if regular else []) if m not in needed]
+        file_world = maps_file_env(cfg['maps'], needed, cfg['device'], load_lanegraph=True)
+    if not regular:
+        run_planner_eval(PlannerConfig(**plan_cfg_dict), None, file_world or SyntheticLaneWorld(), cfg['dt'], cfg['device'], cfg['out'], None, None,
                          scenario_dir=cfg['scenario_dir'], skip_regular=True, eval_replay_planner=cfg['eval_replay_planner'],
                          batch_scenes=cfg['batch_scenes'])
         return
     # regular scenes: every window of the tracks file, one scene per item as the reference's loader of batch size 1 yields them
     from . import synth
     from .datasets.nuscenes_dataset import NuScenesDataset
-    raster, dx = synth.make_raster(M=MAX_MAPS_PER_CALL)
-    world = synth.SyntheticMapEnv(raster, dx, lane_graph=synth.make_lane_graph()).to(cfg['device'])
+    if file_world is not None:
+        world = file_world
+    else:
+        raster, dx = synth.make_raster(M=MAX_MAPS_PER_CALL)
+        world = synth.SyntheticMapEnv(raster, dx, lane_graph=synth.make_lane_graph()).to(cfg['device'])
     ds = NuScenesDataset(cfg['tracks'], world, device=cfg['device'])
     run_planner_eval(PlannerConfig(**plan_cfg_dict), ds.loader(1), world, cfg['dt'], cfg['device'], cfg['out'], ds.get_state_normalizer(),
                      ds.get_att_normalizer(), scenario_dir=cfg['scenario_dir'], skip_regular=False,

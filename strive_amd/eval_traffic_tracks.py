@@ -5,8 +5,8 @@
 takes test_traffic's arguments and writes the same report to ``OUT/test_log.txt``; the options that describe synthetic scenes
 (``--scenes``, ``--num_scenes``, ``--scene_sizes``, ``--seed``) are refused.  It is a module of its own because
 ``strive_amd/test_traffic.py`` is one of the files every change here is measured with and therefore stays as it is; all it adds to
-that file's ``main`` is where the loader comes from.  The scenes live on the maps of ``synth.make_raster`` that the file names
-('synthetic-<m>'); batches come from ``NuScenesDataset.loader`` (datasets/nuscenes_dataset.py), assembled on the device; the model
+that file's ``main`` is where the loader comes from.  The scenes live on the maps of ``--maps FILE`` (a maps file, datasets/maps.py)
+or, without it, on the maps of ``synth.make_raster`` that the tracks file names ('synthetic-<m>'); batches come from ``NuScenesDataset.loader`` (datasets/nuscenes_dataset.py), assembled on the device; the model
 takes the dataset's normalisers.
 """
 import os
@@ -20,8 +20,44 @@ from . import test_traffic as TT
 SYNTHETIC_ONLY = ('scenes', 'num_scenes', 'scene_sizes', 'seed')
 
 
+def maps_file_env(path, needed, device, load_lanegraph=False):
+    """Map environment of ``--maps FILE`` (datasets/maps.py ``map_env_from_file``: rasters and, with ``load_lanegraph``, lane graphs
+    built on the device).  ``needed``: the map names the scenes carry; one that the file lacks ends the run with a message naming it."""
+    from .datasets.maps import load_maps, map_env_from_file
+    try:
+        mf = load_maps(path)
+    except ValueError as e:
+        raise SystemExit('--maps: %s' % e)
+    for name in needed:
+        if name not in mf.names:
+            raise SystemExit('--maps %s has no map named %r (it holds: %s)' % (path, name, ', '.join(mf.names)))
+    return map_env_from_file(mf, load_lanegraph=load_lanegraph, device=device)
+
+
+def scenario_map_names(*dirs):
+    """The map names of the scenario files (``*.json``) in the directories, in order of appearance; a missing directory has none."""
+    import glob
+    import json
+    names = []
+    for d in dirs:
+        for path in sorted(glob.glob(os.path.join(d, '*.json'))):
+            with open(path, 'r') as f:
+                jd = json.load(f)
+            if jd is not None and jd['map'] not in names:
+                names.append(jd['map'])
+    return names
+
+
+def one_map_source(cfg, other):
+    """``--maps`` and the driver's synthetic world (``--map_world`` / ``--lane_world``) both name the map environment."""
+    if cfg.get('maps') is not None and cfg.get(other) is not None:
+        raise SystemExit('--maps and --%s both name the map environment: pass one of them' % other)
+
+
 def tracks_loader(cfg, device):
-    """(loader, map_env) of ``cfg['tracks']`` and / or ``cfg['scenario_path']``; ``loader.dataset`` is the NuScenesDataset."""
+    """(loader, map_env) of ``cfg['tracks']`` and / or ``cfg['scenario_path']``; ``loader.dataset`` is the NuScenesDataset.  The maps
+    are those of ``cfg['maps']`` (a maps file, datasets/maps.py; lane graphs with ``cfg['load_lanegraph']``) or, without it, the
+    synthetic ones."""
     from . import synth
     from .datasets.nuscenes_dataset import NuScenesDataset
     from .datasets.tracks import load_tracks
@@ -36,9 +72,12 @@ def tracks_loader(cfg, device):
     maps = list(tr['scene_map']) if tr is not None else []
     if cfg.get('scenario_path') is not None:
         maps += [sc['map'] for sc in read_adv_scenes(cfg['scenario_path'])]
-    nmaps = 1 + max([int(m.rsplit('-', 1)[1]) for m in maps if m.startswith('synthetic-')] + [0])
-    raster, dx = synth.make_raster(M=nmaps)
-    map_env = synth.SyntheticMapEnv(raster, dx).to(device)
+    if cfg.get('maps') is not None:
+        map_env = maps_file_env(cfg['maps'], maps, device, load_lanegraph=bool(cfg.get('load_lanegraph', False)))
+    else:
+        nmaps = 1 + max([int(m.rsplit('-', 1)[1]) for m in maps if m.startswith('synthetic-')] + [0])
+        raster, dx = synth.make_raster(M=nmaps)
+        map_env = synth.SyntheticMapEnv(raster, dx).to(device)
     ds = NuScenesDataset(tr, map_env, categories=cats, npast=cfg.get('past_len', 4), nfuture=cfg.get('future_len', 12),
                          seq_interval=cfg.get('seq_interval', 1), scenario_path=cfg.get('scenario_path'), device=device)
     return ds.loader(cfg.get('batch_size', 8)), map_env
@@ -51,6 +90,7 @@ def get_parser():
         a.help, a.default = 'not used here', None
     p.add_argument('--tracks', type=str, default=None, help='the tracks file (datasets/tracks.py)')
     p.add_argument('--scenario_path', type=str, default=None, help='a directory of scenario files appended to the scenes')
+    p.add_argument('--maps', type=str, default=None, help='a maps file (datasets/maps.py) with the maps the scenes name; default: the synthetic maps')
     return p
 
 

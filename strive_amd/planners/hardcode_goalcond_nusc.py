@@ -190,6 +190,7 @@ class HardcodeNuscPlanner(PlannerNusc):
             raise ValueError('every scene needs an ego at position %d' % self.ego_idx)
         ptr = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
         self.batch_maps = [self.map_env.map_list[int(map_idx[b])] for b in range(self.B)]
+        from ..datasets.maps import DeviceLaneGraph
         names = sorted(set(self.batch_maps), key=self.batch_maps.index)
         if len(names) > 4:
             raise NotImplementedError('at most 4 maps per batch (nuScenes has 4)')
@@ -198,7 +199,11 @@ class HardcodeNuscPlanner(PlannerNusc):
             key = (name, float(self.cfg.xydistmax), str(dev))
             g = self._graphs.get(key)
             if g is None:
-                g = PackedLaneGraph(self.lane_graphs[name], self.cfg.xydistmax, dev)
+                lg = self.lane_graphs[name]
+                if isinstance(lg, DeviceLaneGraph):          # built on the device (a maps file): its tables never visit the host
+                    g = lg.packed(self.cfg.xydistmax, dev)
+                else:
+                    g = PackedLaneGraph(lg, self.cfg.xydistmax, dev)
                 self._graphs[key] = g
             graphs.append(g)
         self._world = dict(

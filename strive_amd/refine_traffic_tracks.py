@@ -327,6 +327,7 @@ ARGUMENTS = (
     ('num_classes', int, 2, 'number of agent categories when --agent_types is not given'),
     ('tracks', str, None, 'tracks file (datasets/tracks.py) to take the scenes from'),
     ('scenario_path', str, None, 'a directory of scenario files appended to the scenes'),
+    ('maps', str, None, 'a maps file (datasets/maps.py) with the maps the scenes name; default: the synthetic maps'),
     ('seq_interval', int, 10, 'steps from the start of one window of a scene to the start of the next'),
     ('shuffle', bool, False, 'walk the scenes in a random order (drawn from --seed)'),
     ('feasibility_num', int, 1, 'a scene with fewer agents is skipped'),
@@ -416,7 +417,7 @@ def main(argv=None, keep_results=False):
         device = torch.device(cfg['device'])
         _log(log, 'Using device %s...' % str(device))
         torch.manual_seed(cfg['seed'])
-        loader, map_env = tracks_loader({k: cfg[k] for k in ('tracks', 'scenario_path', 'num_classes', 'past_len', 'future_len',
+        loader, map_env = tracks_loader({k: cfg[k] for k in ('tracks', 'scenario_path', 'maps', 'num_classes', 'past_len', 'future_len',
                                                              'seq_interval')}, device)
         dataset = loader.dataset
         source = scene_source(dataset, cfg['shuffle'], torch.Generator().manual_seed(cfg['seed']))

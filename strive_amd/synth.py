@@ -377,10 +377,11 @@ def assemble_lane_graph(lanes, outgoing):
             'edgeixes': np.asarray(edgeixes, dtype=np.int64), 'ee2ix': ee2ix}
 
 
-def make_lane_graph(extent=256.0, period=40.0, centre=9.0, lane_off=3.0, step=2.0):
-    """Lane graph of the synthetic raster (`make_raster`, map 0: roads of width 18 m every 40 m in both directions): one
+def make_lanes(extent=256.0, period=40.0, centre=9.0, lane_off=3.0, step=2.0):
+    """Lanes of the synthetic raster (`make_raster`, map 0: roads of width 18 m every 40 m in both directions): one
     lane per direction on every road, cut into segments at the crossings; at a crossing every arriving segment continues
-    straight (first connection) and turns right (second connection), so node out-degrees of 2 and in-degrees of 2 occur."""
+    straight (first connection) and turns right (second connection), so node out-degrees of 2 and in-degrees of 2 occur.
+    -> (lanes: list of (k, 2) polylines, outgoing: per lane the lanes that continue it)."""
     cs = [c for c in np.arange(centre, extent, period)]
     cuts = [0.0] + cs + [extent]            # segment borders along a road: the crossing road centres
 
@@ -425,7 +426,12 @@ def make_lane_graph(extent=256.0, period=40.0, centre=9.0, lane_off=3.0, step=2.
                     key = ('h', ci, td, tseg)
                 if key in index:
                     outgoing[i].append(index[key])
-    return assemble_lane_graph(lanes, outgoing)
+    return lanes, outgoing
+
+
+def make_lane_graph(extent=256.0, period=40.0, centre=9.0, lane_off=3.0, step=2.0):
+    """Lane graph of the synthetic raster: `make_lanes` assembled into the lane-graph dict."""
+    return assemble_lane_graph(*make_lanes(extent, period, centre, lane_off, step))
 
 
 def lane_scene_poses(lane_graph, n, key, radius=35.0, centre=(128.0, 128.0), min_gap=6.0, speed=(2.0, 8.0)):
@@ -449,3 +455,57 @@ def lane_scene_poses(lane_graph, n, key, radius=35.0, centre=(128.0, 128.0), min
     h = np.arctan2(hd[:, 1], hd[:, 0])
     s = counter_uniform((n,), key + '/ls', speed[0], speed[1])
     return px, py, h, s
+
+
+# --------------------------------------------------------------------------------------------
+# maps file (strive_amd/datasets/maps.py)
+# --------------------------------------------------------------------------------------------
+
+def dirty_lanes(lanes, outgoing):
+    """What an exporter's discretisation hands over before cleaning: every third lane repeats a point in its middle, every
+    fourth ends in a repeated point (duplicate removal), and every lane with a successor ends ON its first successor's first
+    point (trimming at connections); dead ends list a token that has no lane (-1).  Cleaning gives back ``lanes``.
+    -> (lanes, outgoing, incoming), incoming in lane order like the devkit's connectivity."""
+    out = []
+    for i, ln in enumerate(lanes):
+        p = [np.asarray(ln, dtype=np.float64)]
+        if i % 3 == 0 and len(ln) > 2:
+            k = len(ln) // 2
+            p = [ln[:k + 1], ln[k:k + 1], ln[k + 1:]]
+        if i % 4 == 1:
+            p.append(ln[-1:])
+        if outgoing[i]:
+            p.append(np.asarray(lanes[outgoing[i][0]], dtype=np.float64)[:1])
+        out.append(np.concatenate(p, axis=0))
+    incoming = [[] for _ in lanes]
+    for j, o in enumerate(outgoing):
+        for i in o:
+            incoming[i].append(j)
+    outgoing = [list(o) if o else [-1] for o in outgoing]
+    return out, outgoing, incoming
+
+
+def make_maps_file(path, names=('boston-seaport', 'singapore-onenorth'), extent=256.0, period=40.0, centre=9.0, lane_off=3.0, step=2.0,
+                   road_half_width=9.0):
+    """Write a synthetic maps file (strive_amd/datasets/maps.py) and return the ``maps`` dict that went into it.  Every map is the
+    world of `make_raster` / `make_lanes`: the drivable area is one polygon, the map's square with the blocks between the roads
+    as holes; a road divider runs along every road centre, a carpark polygon sits in the first block; the lanes follow the roads
+    and arrive as `dirty_lanes` leaves them.  The default names give one map that is flipped (singapore) and one that is not."""
+    from .datasets.maps import save_maps
+    cs = [float(c) for c in np.arange(centre, extent, period)]
+    edges = [0.0] + [v for c in cs for v in (c - road_half_width, c + road_half_width)] + [extent]
+    blocks = [(a, b) for a, b in zip(edges[2::2], edges[3::2]) if b - a > 1e-9]          # the gaps between consecutive roads
+    square = lambda x0, y0, x1, y1: np.array([[x0, y0], [x1, y0], [x1, y1], [x0, y1]], dtype=np.float64)
+    holes = [square(x0, y0, x1, y1) for (y0, y1) in blocks for (x0, x1) in blocks]
+    dividers = [np.array([[0.0, c], [extent, c]]) for c in cs] + [np.array([[c, 0.0], [c, extent]]) for c in cs]
+    (bx0, bx1) = blocks[0]
+    carpark = [[square(bx0 + 2.0, bx0 + 2.0, bx1 - 2.0, bx1 - 2.0), square(bx0 + 6.0, bx0 + 6.0, bx0 + 10.0, bx0 + 10.0)]]
+    lanes, outgoing, incoming = dirty_lanes(*make_lanes(extent, period, centre, lane_off, step))
+    maps = {}
+    for name in names:
+        maps[name] = {'size': (float(extent), float(extent)),
+                      'layers': {'drivable_area': [[square(0.0, 0.0, extent, extent)] + holes], 'carpark_area': carpark,
+                                 'road_divider': dividers, 'lane_divider': dividers[:1]},
+                      'lanes': lanes, 'outgoing': outgoing, 'incoming': incoming}
+    save_maps(path, maps)
+    return maps

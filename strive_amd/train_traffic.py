@@ -46,6 +46,7 @@ ARGUMENTS = (
     ('tracks', str, None, 'tracks file (datasets/tracks.py) to train on'),
     ('val_tracks', str, None, 'tracks file to validate on; leave out to train without validation'),
     ('scenario_dir', str, None, 'directory of scenario files appended to the training windows'),
+    ('maps', str, None, 'a maps file (datasets/maps.py) with the maps both tracks files name; default: the synthetic maps'),
     ('data_noise_std', float, 0.0, 'sigma of the Gaussian noise on the observed states of training batches'),
     ('epochs', int, 200, 'index of the last epoch + 1'),
     ('val_every', int, 3, 'validate in every epoch divisible by this'),
@@ -309,6 +310,7 @@ def open_data(cfg, device):
     """(training loader, its maps, validation loader or None, its maps) from the tracks files of ``cfg``"""
     from .eval_traffic_tracks import tracks_loader
     shape = {k: cfg[k] for k in ('num_classes', 'past_len', 'future_len', 'batch_size')}
+    shape['maps'] = cfg.get('maps')
     plain, maps = tracks_loader(dict(shape, tracks=cfg['tracks'], scenario_path=cfg['scenario_dir']), device)
     ds = plain.dataset
     ds.noise_std = cfg['data_noise_std']

@@ -102,6 +102,7 @@ def get_parser():
     p.add_argument('--viz_video', action='store_true', help='also render one frame per step')
     p.add_argument('--mp4', action='store_true', help='turn the frames into .mp4 with ffmpeg and remove them')
     p.add_argument('--map_world', type=str, default=None, choices=['synthetic'], help='map environment with the rasters')
+    p.add_argument('--maps', type=str, default=None, help='a maps file (datasets/maps.py) with the maps the scenes name, instead of --map_world')
     p.add_argument('--device', type=str, default='cuda:0')
     p.add_argument('--L', type=int, default=720, help='picture edge in pixels')
     p.add_argument('--batch_scenes', type=int, default=36, help='scenes per kernel launch')
@@ -111,7 +112,9 @@ def get_parser():
 def main(argv=None):
     cfg = vars(get_parser().parse_args(argv))
     render.check_ffmpeg(cfg['mp4'])
-    if cfg['map_world'] is None:
+    from .eval_traffic_tracks import maps_file_env, one_map_source, scenario_map_names
+    one_map_source(cfg, 'map_world')
+    if cfg['map_world'] is None and cfg['maps'] is None:
         raise SystemExit('viz_adv_gen: the nuScenes devkit and data are not available here; pass a map environment from Python '
                          '(qual_eval(scenarios, viz_res, viz_stage, map_env, out)) or use --map_world synthetic')
     if not os.path.exists(cfg['scenarios']):
@@ -121,7 +124,11 @@ def main(argv=None):
     for resname in cfg['viz_res']:
         res_path = os.path.join(cfg['scenarios'], resname)
         scenarios[resname] = read_adv_scenes(res_path) if os.path.exists(res_path) else []
-    return qual_eval(scenarios, cfg['viz_res'], cfg['viz_stage'], synthetic_map_world(cfg['device']), cfg['out'],
+    if cfg['maps'] is not None:
+        world = maps_file_env(cfg['maps'], scenario_map_names(*[os.path.join(cfg['scenarios'], r) for r in cfg['viz_res']]), cfg['device'])
+    else:
+        world = synthetic_map_world(cfg['device'])
+    return qual_eval(scenarios, cfg['viz_res'], cfg['viz_stage'], world, cfg['out'],
                      viz_video=cfg['viz_video'], L=cfg['L'], batch_scenes=cfg['batch_scenes'], mp4=cfg['mp4'])
 
 

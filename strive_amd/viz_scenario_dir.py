@@ -80,6 +80,7 @@ def get_parser():
     p.add_argument('--viz_video', action='store_true', help='also render one frame per step')
     p.add_argument('--mp4', action='store_true', help='turn the frames into <out>_vid_000.mp4 with ffmpeg and remove them')
     p.add_argument('--map_world', type=str, default=None, choices=['synthetic'], help='map environment with the rasters')
+    p.add_argument('--maps', type=str, default=None, help='a maps file (datasets/maps.py) with the maps the scenes name, instead of --map_world')
     p.add_argument('--device', type=str, default='cuda:0')
     p.add_argument('--L', type=int, default=720, help='picture edge in pixels')
     p.add_argument('--batch_scenes', type=int, default=36, help='scenes per kernel launch')
@@ -93,10 +94,14 @@ def parse_cfg(argv=None):
 def main(argv=None):
     cfg = parse_cfg(argv)
     render.check_ffmpeg(cfg['mp4'])
-    if cfg['map_world'] is None:
+    from .eval_traffic_tracks import maps_file_env, one_map_source, scenario_map_names
+    one_map_source(cfg, 'map_world')
+    if cfg['map_world'] is None and cfg['maps'] is None:
         raise SystemExit('viz_scenario_dir: the nuScenes devkit and data are not available here; pass a map environment from Python '
                          '(viz_scenario_dir(cfg, map_env)) or use --map_world synthetic')
     print('Args: ' + str(cfg))
+    if cfg['maps'] is not None:
+        return viz_scenario_dir(cfg, maps_file_env(cfg['maps'], scenario_map_names(cfg['scenarios']), cfg['device']))
     return viz_scenario_dir(cfg)
 
 
