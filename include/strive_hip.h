@@ -1045,6 +1045,99 @@ typedef struct StriveRenderJob {
 
 int strive_render_pictures(const StriveMap* map, const StriveRenderJob* job, uint8_t* out, strive_stream_t stream);
 
+/* The tables strive_render_pictures reads (pose, mapix, prim_range, prims, verts), built on the device from a batch that lives
+ * there, for any number of VIEWS in one launch and without a host synchronisation: what the reference's viz_scene_graph
+ * (reference src/datasets/nuscenes_utils.py:477-621) hands to viz_map_crop / viz_map_crop_video (:632-653), followed by the
+ * artists render_obj_observation (:733-835) makes of it.  One workgroup per picture (grid-stride), no atomics, ordinary stores;
+ * in-picture offsets by a workgroup scan.  The bytes a picture's slots receive depend on its own scene and view only.
+ *
+ * Inputs, all NORMALISED and only read: past_gt (NA, PT, past_stride >= 4), future_gt (NA, FT, future_stride >= 4), lw (NA, 2),
+ * ow_gt (NA, FT, 4) or NULL, up to STRIVE_SCENE_DRAW_PREDS prediction sets pred[i] (NA, pred_NS[i], pred_FPT[i], 4);
+ * scene_ptr (B + 1) agent offsets; map_idx (B) int64.  DEVIATION: the reference unnormalises the caller's graph in place and
+ * normalises it back, which changes last bits of the caller's batch; here every value is unnormalised in registers with
+ * MeanStdNormalizer.unnormalize's two fp32 operations (one rounded multiply, one rounded add) and the batch is never written.
+ *
+ * A view = one viz_scene_graph call's picture set, an int32 record of STRIVE_SCENE_DRAW_VIEW_INTS:
+ *   [0] bidx   [1] flags (below)   [2] [3] first drawn agent (scene-local) and count: (0, n), or (aidx, 1)
+ *   [4] [5] first ground-truth agent and count (0: no ground-truth pass): show_gt / show_gt_idx / aidx resolved by the host
+ *   [6] crop_t   [7] prediction set, -1: future_gt is drawn (NS = 1)   [8] first row of this view's marker colours in `rainbow`
+ *   [9] first row of its styles in `style`, -1: the defaults   [10..15] unused
+ * and a float record view_f (4): bounds[0], bounds[1], L / (bounds[2] - bounds[0]), W / (bounds[3] - bounds[1]) (host doubles,
+ * rounded to fp32 as numpy does for objs2crop).  QUIRK KEPT: with aidx the reference slices crop_objs but neither crop_lw nor
+ * the colours, so the drawn agent takes row 0's size, colour and style: sizes and styles are indexed by the POSITION in the
+ * drawn list, trajectories by the agent.
+ *
+ * A picture = an int32 record of STRIVE_SCENE_DRAW_PIC_INTS: [0] view  [1] sample s, -1: the overview (all samples, all steps)
+ * [2] step t (frame (s, t) of viz_map_crop_video holds car_kin[:, s:s+1, t:t+1], T = 1, no ground-truth pass)
+ * [3] first primitive slot  [4] first vertex slot  [5] primitive capacity  [6] vertex capacity  [7] unused.
+ * Capacities come from shapes, on the host; NaNs only shrink a picture's count; prim_range[f] = [slot, slot + count).
+ *
+ * Crop pose (x, y, hx, hy), unnormalised: past_gt[first agent of the scene, PT - 1]; with STRIVE_SCENE_DRAW_CROP_T the same
+ * agent's row crop_t of past_gt (crop_t < PT) or future_gt; with STRIVE_SCENE_DRAW_CENTER ((mx, my), 1, 0), (mx, my) the mean
+ * over the scene's agents n, samples s and steps t (past, repeated per sample, then the drawn future) of every position without
+ * a NaN: partial sums in float64, thread i of 256 taking items i, i + 256, ... of the (n, s, t) order, then a fixed binary tree;
+ * divided in float64, rounded once.  It depends on nothing outside the scene.
+ *
+ * Frame: objs2crop (reference src/datasets/map_env.py:231-254 with objects2frame) in fp32, unfused: theta = atan2(hy_c, hx_c);
+ * (x', y') = ((x - x_c) cos + (y - y_c) sin, (y - y_c) cos - (x - x_c) sin); heading (cos, sin)(atan2(hy, hx) - theta);
+ * x' = (x' - b0) sl, y' = (y' - b1) sw; sizes l sl, w sw.
+ *
+ * Records, in matplotlib's draw order: discs (markers, z 1), polylines (z 2), cars (z 3); inside a group the ground-truth pass
+ * (white lines and cars, alpha 0.7, width 1, size 8, no initial car) before the prediction pass; inside a pass agents, then
+ * samples, then steps.  A step with a NaN in its four crop values is left out BEFORE vertices and markers are emitted, so a line
+ * joins across a gap; a trajectory without a step gives no line.  With STRIVE_SCENE_DRAW_TRAJ: one disc per step in
+ * rainbow[row + t] (the host's gist_rainbow(linspace(0, 1, T)); T = PT + FT for the ground truth at rb_gt_off, T = 1 for a frame
+ * at rb_one_off), diameter (sqrt(size) + 1) k; one polyline per trajectory, width linewidth k, its vertices the discs' centres;
+ * one car per drawn agent at the first step of sample 0 (of the frame's sample) whose crop x is not NaN -- an agent without one
+ * sets STRIVE_SCENE_DRAW_NO_STEP (the reference raises IndexError, :801, :810) and gets no car.  Without it: one car per step
+ * without a NaN, alpha = the agent's at t = 0 and 0.1 + (1 - t / T) 0.2 after, evaluated in float64 and rounded once.  Styles:
+ * style (rows, 8) fp32 r, g, b, alpha, line width, marker size, 2 unused; default colour cycle_rgb[position % 9], 0.7, 1.0, 8.0.
+ * k (float64): picture pixels per point; products with k are formed in float64 and rounded once, as the host path's.
+ *
+ * status (F) int32 per picture (one word per picture, not per view: pictures of a view are written by different workgroups
+ * and nothing is atomic; the host ORs them): bits below, and with NO_STEP (position of the first such agent + 1) << 8.  A
+ * picture with BAD_VIEW (a record that does not fit the shapes) gets an empty range and a NaN pose. */
+#define STRIVE_SCENE_DRAW_PREDS 4
+#define STRIVE_SCENE_DRAW_VIEW_INTS 16
+#define STRIVE_SCENE_DRAW_PIC_INTS 8
+#define STRIVE_SCENE_DRAW_TRAJ 1          /* viz_traj */
+#define STRIVE_SCENE_DRAW_CENTER 2        /* center_viz */
+#define STRIVE_SCENE_DRAW_CROP_T 4        /* crop_t given */
+#define STRIVE_SCENE_DRAW_OW_GT 8         /* the ground-truth pass draws ow_gt */
+#define STRIVE_SCENE_DRAW_BAD_MAP 1       /* map_idx[bidx] outside [0, M) */
+#define STRIVE_SCENE_DRAW_NO_STEP 2       /* an agent with no observed step where the reference raises IndexError */
+#define STRIVE_SCENE_DRAW_BAD_CROP_T 4    /* crop_t outside [0, PT + FT) */
+#define STRIVE_SCENE_DRAW_BAD_VIEW 8      /* a view or picture record that does not fit the shapes */
+typedef struct StriveSceneDraw {
+    const float* past_gt;
+    const float* future_gt;
+    const float* lw;
+    const float* ow_gt;
+    const float* pred[STRIVE_SCENE_DRAW_PREDS];
+    const int32_t* scene_ptr;     /* (B + 1) */
+    const int64_t* map_idx;       /* (B) */
+    const int32_t* views;         /* (NVIEW, STRIVE_SCENE_DRAW_VIEW_INTS) */
+    const float* view_f;          /* (NVIEW, 4) */
+    const int32_t* pictures;      /* (F, STRIVE_SCENE_DRAW_PIC_INTS) */
+    const float* style;           /* (style_rows, 8) or NULL */
+    const float* rainbow;         /* (rb_rows, 3) */
+    float* pose;                  /* out (F, 4) */
+    int32_t* mapix;               /* out (F) */
+    int32_t* prim_range;          /* out (F, 2) */
+    float* prims;                 /* out (NP, STRIVE_RENDER_PRIM_FLOATS), 16-byte aligned */
+    float* verts;                 /* out (NV, 2) */
+    int32_t* status;              /* out (F) */
+    double k;
+    int32_t NA, B, M, PT, FT, past_stride, future_stride, NVIEW, F, NP, NV;
+    int32_t rb_rows, rb_gt_off, rb_one_off, style_rows;
+    int32_t pred_NS[STRIVE_SCENE_DRAW_PREDS], pred_FPT[STRIVE_SCENE_DRAW_PREDS];
+    float edge_px, heading_px;
+    float cycle_rgb[27];
+    StriveNorm norm;
+} StriveSceneDraw;
+
+int strive_scene_draw_tables(const StriveSceneDraw* job, strive_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Lane graphs built on the device (reference src/datasets/nuscenes_utils.py:28-122: remove_duplicates, process_lanegraph,
  * process_edges; the Singapore flip of src/datasets/map_env.py:131-144) and the planner's tables of them (StrivePlannerMap).

@@ -147,6 +147,22 @@ class StriveRenderJob(C.Structure):
                 ('layer_rgb', C.c_float * 18), ('layer_alpha', C.c_float * 6)]
 
 
+class StriveNorm(C.Structure):
+    _fields_ = [('state_mean', C.c_float * 6), ('state_std', C.c_float * 6), ('att_mean', C.c_float * 2), ('att_std', C.c_float * 2)]
+
+
+class StriveSceneDraw(C.Structure):
+    _fields_ = [('past_gt', C.c_void_p), ('future_gt', C.c_void_p), ('lw', C.c_void_p), ('ow_gt', C.c_void_p), ('pred', C.c_void_p * 4),
+                ('scene_ptr', C.c_void_p), ('map_idx', C.c_void_p), ('views', C.c_void_p), ('view_f', C.c_void_p), ('pictures', C.c_void_p),
+                ('style', C.c_void_p), ('rainbow', C.c_void_p), ('pose', C.c_void_p), ('mapix', C.c_void_p), ('prim_range', C.c_void_p),
+                ('prims', C.c_void_p), ('verts', C.c_void_p), ('status', C.c_void_p), ('k', C.c_double),
+                ('NA', C.c_int32), ('B', C.c_int32), ('M', C.c_int32), ('PT', C.c_int32), ('FT', C.c_int32), ('past_stride', C.c_int32),
+                ('future_stride', C.c_int32), ('NVIEW', C.c_int32), ('F', C.c_int32), ('NP', C.c_int32), ('NV', C.c_int32),
+                ('rb_rows', C.c_int32), ('rb_gt_off', C.c_int32), ('rb_one_off', C.c_int32), ('style_rows', C.c_int32),
+                ('pred_NS', C.c_int32 * 4), ('pred_FPT', C.c_int32 * 4), ('edge_px', C.c_float), ('heading_px', C.c_float),
+                ('cycle_rgb', C.c_float * 27), ('norm', StriveNorm)]
+
+
 class StriveLaneGraphIn(C.Structure):
     _fields_ = [('pts', C.c_void_p), ('lane_ptr', C.c_void_p), ('out_ptr', C.c_void_p), ('out_idx', C.c_void_p), ('in_ptr', C.c_void_p),
                 ('in_idx', C.c_void_p), ('NL', C.c_int32), ('P', C.c_int32), ('flip', C.c_int32), ('reserved', C.c_int32),
@@ -161,10 +177,6 @@ class StriveLaneGraphOut(C.Structure):
 
 class StriveEdgeGridRec(C.Structure):
     _fields_ = [('gx0', C.c_double), ('gy0', C.c_double), ('total', C.c_int64), ('gnx', C.c_int32), ('gny', C.c_int32)]
-
-
-class StriveNorm(C.Structure):
-    _fields_ = [('state_mean', C.c_float * 6), ('state_std', C.c_float * 6), ('att_mean', C.c_float * 2), ('att_std', C.c_float * 2)]
 
 
 P = C.c_void_p
@@ -265,6 +277,7 @@ PROTOTYPES = {
     'strive_adam_flat': (C.c_int, [P, P, P, P, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
                                    C.c_double, P, I, P, P]),
     'strive_render_pictures': (C.c_int, [C.POINTER(StriveMap), C.POINTER(StriveRenderJob), P, P]),
+    'strive_scene_draw_tables': (C.c_int, [C.POINTER(StriveSceneDraw), P]),
     'strive_lane_graph_workspace_bytes': (SZ, [I, I]),
     'strive_lane_graph_count': (C.c_int, [C.POINTER(StriveLaneGraphIn), P, SZ, P, P]),
     'strive_lane_graph_fill': (C.c_int, [C.POINTER(StriveLaneGraphIn), P, SZ, C.POINTER(StriveLaneGraphOut), P]),

@@ -7,6 +7,12 @@ import torch
 from .. import ops
 
 
+# The names strive_amd.dropin lays over the reference's datasets/nuscenes_utils.py.  The picture functions at the end of this file
+# are not among them: next to a reference checkout its own matplotlib functions keep drawing.
+__all__ = ['angle_diff', 'heading_change_rate', 'velocity', 'gen_car_coords', 'get_map_obs', 'get_coll_point', 'check_on_layer',
+           'check_line_layer']
+
+
 class _RawEnv(object):
     def __init__(self, maps, dx, bounds, L, W):
         self.nusc_raster, self.nusc_dx, self.bounds, self.L, self.W = maps, dx, list(bounds), L, W
@@ -120,3 +126,50 @@ def check_line_layer(drivables, dx, start, end, mapixes):
     pix = torch.round(pts / dx[mapixes].view(B, 1, 2)).long()
     m = mapixes.view(B, 1).expand(B, n)
     return torch.sum(drivables[m, pix[..., 1], pix[..., 0]] == 0, dim=-1) > 0
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# pictures of a live batch (reference :477-653)
+# ------------------------------------------------------------------------------------------------------------------------
+
+def create_video(img_path_form, out_path, fps):
+    """The reference's ffmpeg command (:623-630), in a fresh child process."""
+    import subprocess
+    subprocess.run(['ffmpeg', '-y', '-r', str(fps), '-i', img_path_form, '-vcodec', 'libx264', '-crf', '18', '-pix_fmt', 'yuv420p', out_path])
+
+
+def viz_scene_graphs(scene_graph, map_idx, map_env, calls, state_normalizer, att_normalizer, mp4=False, fps=2, workers=None, log=print,
+                     ptr=None):
+    """Any number of ``viz_scene_graph`` calls on ONE batch -- ``calls``: dicts of that function's arguments from ``bidx`` on
+    (``bidx`` and ``out_path`` required) -- served by ONE table launch (strive_scene_draw_tables), ONE render launch and ONE
+    read-back; then the PNG files are written on a thread pool (render.write_pngs).  The batch is not written.  -> the number of
+    pictures.  ``ptr``: the batch's scene offsets on the host, where the caller has them (otherwise the batch's own host copy, or
+    one read-back).  ``mp4``: run the reference's ffmpeg command per frame directory and remove the frames, as the reference does;
+    without it the frames stay as PNG files."""
+    import shutil
+    from .. import render, scene_draw
+    render.check_ffmpeg(mp4)
+    paths, pictures, videos = scene_draw.draw_calls(scene_graph, map_idx, map_env, calls, state_normalizer, att_normalizer, ptr=ptr)
+    for path in paths:
+        log('saving %s' % path)
+    render.write_pngs(paths, pictures, workers)
+    if mp4:
+        import os
+        for vdir in videos:
+            create_video(os.path.join(vdir, 'frame%04d.png'), vdir + '.mp4', fps)
+            shutil.rmtree(vdir)
+    return len(paths)
+
+
+def viz_scene_graph(scene_graph, map_idx, map_env, bidx, out_path, state_normalizer, att_normalizer, future_pred=None, aidx=None,
+                    viz_traj=False, make_video=True, show_gt=False, traj_color_val=None, traj_color_bounds=None,
+                    viz_bounds=[-17.0, -38.5, 60.0, 38.5], center_viz=False, car_colors=None, show_gt_idx=None, crop_t=None, ow_gt=None,
+                    mp4=False):
+    """Pictures of scene ``bidx`` of a NORMALISED batch (reference :477-621, same arguments and defaults): ``<out_path>.png`` and,
+    with ``make_video``, the frames ``<out_path>_%03d/frame%04d.png`` of every sample (kept as PNG files unless ``mp4``).  Drawn on
+    the device (``viz_scene_graphs`` with one call); the batch is left as it is, where the reference unnormalises it in place and
+    normalises it back.  ``traj_color_val`` / ``traj_color_bounds`` are not offered."""
+    call = dict(bidx=bidx, out_path=out_path, future_pred=future_pred, aidx=aidx, viz_traj=viz_traj, make_video=make_video, show_gt=show_gt,
+                traj_color_val=traj_color_val, traj_color_bounds=traj_color_bounds, viz_bounds=viz_bounds, center_viz=center_viz,
+                car_colors=car_colors, show_gt_idx=show_gt_idx, crop_t=crop_t, ow_gt=ow_gt)
+    return viz_scene_graphs(scene_graph, map_idx, map_env, [call], state_normalizer, att_normalizer, mp4=mp4)

@@ -51,3 +51,12 @@ def refine_traffic_optim(scene_graph, map_idx, map_env, model, loss_weights, num
     with torch.no_grad():
         final = model.decode_embedding(cur_z, embed_info, scene_graph, map_idx, map_env, nfuture=save_future_len)
     return init_future_pred, cur_z, final['future_pred'].unsqueeze(1).clone().detach(), embed_info
+
+
+def viz_optim_results(out_path, scene_graph, map_idx, map_env, model, future_pred, viz_bounds=[-60.0, -60.0, 60.0, 60.0], bidx=0):
+    """Overview and frames of a refined scene (reference src/refine_traffic_optim.py:123-144, same arguments): both
+    viz_scene_graph calls around the scene's centroid, default colours, in one table launch, one render launch and one read-back."""
+    from .datasets import nuscenes_utils as nutils
+    from .utils.scenario_gen import optim_result_calls
+    calls = optim_result_calls(out_path, None, future_pred, None, None, viz_bounds, bidx, None, False, None, colored=False)
+    return nutils.viz_scene_graphs(scene_graph, map_idx, map_env, calls, model.get_normalizer(), model.get_att_normalizer())

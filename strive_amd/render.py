@@ -279,18 +279,55 @@ def render_tables(map_env, crop_kin, mapix, bounds, L_, prims, verts, ranges, no
     job = L.StriveRenderJob()
     job.prims, job.pose, job.verts, job.lin, job.mapix, job.lin_ix, job.prim_range, job.no_map = [base + 4 * o for o in off[:8]]
     job.F, job.L, job.W, job.NP, job.NV = F, L_, L_, prims.shape[0], verts.shape[0]
+    out = torch.empty((F, L_, L_, 3), dtype=torch.uint8, device=dev)
+    _launch(lib, map_env, job, out)
+    return out
+
+
+def _launch(lib, map_env, job, out):
+    """strive_render_pictures over a job whose tables are set: adds the reference's layer colours and the map."""
+    raster = map_env.nusc_raster.contiguous()
+    M, Cc, H, W = raster.shape
     for i in range(MAX_LAYERS):
         rgb = to_rgb(MAP_COLORS[i])
         for c in range(3):
             job.layer_rgb[i * 3 + c] = rgb[c]
         job.layer_alpha[i] = MAP_ALPHAS[i]
     mp = L.StriveMap()
-    raster = raster.contiguous()
-    dx = map_env.nusc_dx.to(dev).contiguous()
+    dx = map_env.nusc_dx.to(raster.device).contiguous()
     mp.raster, mp.dx, mp.M, mp.C, mp.H, mp.W = raster.data_ptr(), dx.data_ptr(), M, Cc, H, W
-    mp.L, mp.Wc = L_, L_
-    out = torch.empty((F, L_, L_, 3), dtype=torch.uint8, device=dev)
+    mp.L, mp.Wc = job.L, job.L
     lib.call('strive_render_pictures', C.byref(mp), C.byref(job), L.ptr(out), L.stream_ptr(out))
+
+
+def render_device_tables(map_env, L_, F, pose, mapix, prim_range, prims, verts, lin, lin_ix, no_map, out=None, W_=None):
+    """One launch of strive_render_pictures over tables that are on the map's device already (strive_scene_draw_tables wrote them):
+    nothing is uploaded and nothing is read.  ``pose`` (F, 4) fp32, ``mapix`` (F) int32, ``prim_range`` (F, 2) int32, ``prims``
+    (NP, 16) fp32 and ``verts`` (NV, 2) fp32 are device tensors; ``lin`` (NB, 2, L) fp32, ``lin_ix`` (F) and ``no_map`` (F) int32 are
+    device tensors or device addresses.  -> ``out`` (F, L, L, 3) uint8, allocated unless given.  A picture whose map index is out
+    of range keeps a white background (the table kernel reports it in the picture's status word)."""
+    if W_ is not None and int(W_) != int(L_):
+        raise ValueError('only square pictures are rendered (L == W): the reference mixes the two axes otherwise')
+    raster = map_env.nusc_raster
+    if raster.shape[1] > MAX_LAYERS:
+        raise ValueError('the map has %d layers; the colour list has %d' % (raster.shape[1], MAX_LAYERS))
+    for name, t in (('pose', pose), ('mapix', mapix), ('prim_range', prim_range), ('prims', prims), ('verts', verts)):
+        if t.device != raster.device or not t.is_contiguous():
+            raise ValueError('%s must be a contiguous tensor on the map\'s device' % name)
+    F, L_ = int(F), int(L_)
+    if tuple(pose.shape) != (F, 4) or mapix.numel() != F or tuple(prim_range.shape) != (F, 2) or prims.dim() != 2 or \
+            prims.shape[1] != PRIM_FLOATS or verts.dim() != 2 or verts.shape[1] != 2:
+        raise ValueError('the tables do not have the shapes of %d pictures' % F)
+    if out is None:
+        out = torch.empty((F, L_, L_, 3), dtype=torch.uint8, device=raster.device)
+    elif out.device != raster.device or out.dtype != torch.uint8 or not out.is_contiguous() or out.numel() != F * L_ * L_ * 3:
+        raise ValueError('out is a contiguous (F, L, L, 3) uint8 tensor on the map\'s device')
+    addr = lambda t: t.data_ptr() if torch.is_tensor(t) else int(t)           # noqa: E731
+    job = L.StriveRenderJob()
+    job.pose, job.mapix, job.prim_range, job.prims, job.verts = [t.data_ptr() for t in (pose, mapix, prim_range, prims, verts)]
+    job.lin, job.lin_ix, job.no_map = addr(lin), addr(lin_ix), addr(no_map)
+    job.F, job.L, job.W, job.NP, job.NV = F, L_, L_, prims.shape[0], verts.shape[0]
+    _launch(ops._lib_for(raster), map_env, job, out)
     return out
 
 
@@ -327,6 +364,32 @@ def write_png(path, array, level=3):
     with open(path, 'wb') as f:
         f.write(b'\x89PNG\r\n\x1a\n' + chunk(b'IHDR', struct.pack('>IIBBBBB', W, H, 8, 2, 0, 0, 0)) +
                 chunk(b'IDAT', zlib.compress(rows.tobytes(), level)) + chunk(b'IEND', b''))
+
+
+WRITE_PNG_WORKERS = 8        # measured: tools/scene_draw_bench.py, profiles/r29_scene_draw_bench.json (README)
+
+
+def write_pngs(paths, pictures, workers=None, level=3):
+    """``write_png(paths[i], pictures[i])`` for every i on a pool of ``workers`` threads (zlib releases the interpreter lock while it
+    compresses): the same files, byte for byte.  Missing directories are made.  The default is a fixed small number, never the
+    machine's processor count."""
+    import os
+    from concurrent.futures import ThreadPoolExecutor
+    if len(paths) != len(pictures):
+        raise ValueError('%d paths for %d pictures' % (len(paths), len(pictures)))
+    workers = WRITE_PNG_WORKERS if workers is None else int(workers)
+    if not 1 <= workers <= 16:
+        raise ValueError('write_pngs takes 1 to 16 workers')
+    for d in sorted({os.path.dirname(p) or '.' for p in paths}):
+        os.makedirs(d, exist_ok=True)
+    if workers == 1 or len(paths) <= 1:
+        for p, a in zip(paths, pictures):
+            write_png(p, a, level)
+        return len(paths)
+    with ThreadPoolExecutor(max_workers=workers) as pool:
+        for _ in pool.map(lambda pa: write_png(pa[0], pa[1], level), zip(paths, pictures)):
+            pass
+    return len(paths)
 
 
 # ------------------------------------------------------------------------------------------------------------------------

@@ -151,3 +151,29 @@ def print_metrics(metrics, freq_metrics_cnt, freq_metrics_total, log=print):
         log('%s = %f' % (k, v.mean()))
     for k, v in freq_metrics_cnt.items():
         log('%s = %f' % (k, float(v) / freq_metrics_total[k]))
+
+
+def optim_result_calls(out_path, scene_graph_ptr, future_pred, attack_agt, crop_t, viz_bounds, bidx, ow_gt, show_gt, show_gt_idx,
+                       colored=True):
+    """The two viz_scene_graph calls of viz_optim_results (reference src/utils/scenario_gen.py:160-187): the overview with
+    trajectories, then the frames under ``<out_path>_vid``."""
+    from .. import render
+    colors = None
+    if colored:
+        NA = int(scene_graph_ptr[bidx + 1]) - int(scene_graph_ptr[bidx])
+        colors = render.get_adv_coloring(NA, attack_agt, 0)
+    common = dict(bidx=bidx, future_pred=future_pred, show_gt=show_gt, show_gt_idx=show_gt_idx, viz_bounds=viz_bounds, crop_t=crop_t,
+                  center_viz=crop_t is None, car_colors=colors, ow_gt=ow_gt)
+    return [dict(common, out_path=out_path, viz_traj=True, make_video=False),
+            dict(common, out_path=out_path + '_vid', viz_traj=False, make_video=True)]
+
+
+def viz_optim_results(out_path, scene_graph, map_idx, map_env, model, future_pred, planner_name, attack_agt, crop_t,
+                      viz_bounds=[-60.0, -60.0, 60.0, 60.0], bidx=0, ow_gt=None, show_gt=False, show_gt_idx=None):
+    """Overview and frames of an optimised scene (reference src/utils/scenario_gen.py:149-187, same arguments; ``attack_agt`` is
+    local to scene ``bidx``): both viz_scene_graph calls in one table launch, one render launch and one read-back."""
+    from ..datasets import nuscenes_utils as nutils
+    from ..scene_draw import host_ptr
+    calls = optim_result_calls(out_path, host_ptr(scene_graph), future_pred, attack_agt, crop_t, viz_bounds, bidx, ow_gt, show_gt,
+                               show_gt_idx)
+    return nutils.viz_scene_graphs(scene_graph, map_idx, map_env, calls, model.get_normalizer(), model.get_att_normalizer())
