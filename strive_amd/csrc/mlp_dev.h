@@ -203,7 +203,9 @@ __device__ __forceinline__ void dense_mfma(const float* in, int in_ld, int IN, c
             *reinterpret_cast<uint32_t*>(sb + r * BROW + k2 * 2) = a0 | ((uint32_t)a1 << 16);
             *reinterpret_cast<uint32_t*>(sb + (RB + r) * BROW + k2 * 2) = b0 | ((uint32_t)b1 << 16);
         }
-        if (lane == 0) s_rs[r] = 1.0f / (sc * wscale);            // powers of two: exact
+        // powers of two: exact.  Two factors, not 1 / (sc * wscale): for a row below 2^-97 or so (sc near 2^127) that product is inf
+        // and the row's result was 0 -- a gradient row of 1e-40 came back as zeros instead of to 22 bits of its own largest entry
+        if (lane == 0) s_rs[r] = (1.0f / sc) * (1.0f / wscale);
     }
     __syncthreads();
     // ---- 2. two 16-channel tiles per wave at a time ----
@@ -289,8 +291,9 @@ __device__ __forceinline__ void ln_relu_rows(const float* x, int x_ld, float* y,
         if (h0) { const float d = x0 - mean; v = fmaf(d, d, v); }
         if (h1) { const float d = x1 - mean; v = fmaf(d, d, v); }
         const float rstd = 1.0f / sqrtf(wave_sum(v) / (float)N + LN_EPS);
-        if (h0) y[r * y_ld + c0] = fmaxf((x0 - mean) * rstd * g0 + b0, 0.f);
-        if (h1) y[r * y_ld + c1] = fmaxf((x1 - mean) * rstd * g1 + b1, 0.f);
+        // (not fmaxf: that returns 0 for NaN, and a row with a NaN input came out of the next layer finite -- its bias)
+        if (h0) { const float t = (x0 - mean) * rstd * g0 + b0; y[r * y_ld + c0] = t < 0.f ? 0.f : t; }
+        if (h1) { const float t = (x1 - mean) * rstd * g1 + b1; y[r * y_ld + c1] = t < 0.f ? 0.f : t; }
     }
 }
 
